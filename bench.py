@@ -6,8 +6,17 @@ One step = one frame of the reference's fusion loop (lepard_nicp_test.py:test4):
 TSDF/weight/colour integrate of the new frame. All inputs are device-resident before timing.
 
   python bench.py [--gpus N --steps K --warmup W] [--config 1..5] [--mode replicas|shard]
-                  [--solve replicated|allreduce] [--dims 512] [--nodes 2000]
+                  [--solve replicated|allreduce] [--dims 512] [--nodes 2000] [--full] [--dump-outputs DIR]
 
+A plain run sets up, warms up, times the K steps and prints the result line: the headline figure, the per-frame
+breakdown and the PCG roofline, all read from the timed loop itself.
+--full adds what takes runs of its own after the timed steps: the isolated integrate launches behind
+    `roofline_integrate`, and the `cpu_baseline` legs (oracle port on the host cores; --no-cpu-baseline leaves
+    them out of a --full run).
+--dump-outputs DIR: after the timed steps, what the last timed step returned, as DIR/<name>.npy (f32 / f64):
+    node_rotations, node_translations and solve_status of its solve, and tsdf_sample / color_sample / weight_sample,
+    the fused volume at a fixed seeded sample of voxels (every voxel when the volume has no more than the sample).
+    With --gpus N > 1 rank r writes <name>_rank<r>.npy. The inputs are seeded, so equal arguments give equal inputs.
 --gpus N > 1 without a torch.distributed environment: bench.py starts N ranks itself (a child
     `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ...` running this file,
     started before anything touches the GPU) and exits with its status; under torchrun it checks
@@ -80,7 +89,13 @@ def parse():
     p.add_argument("--matches", type=int, default=10000)
     p.add_argument("--scene-rank", type=int, default=None,
                    help="config 5: run this rank's independent scene (default: the process's own rank)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the isolated integrate launches "
+                        "(roofline_integrate) and the CPU baseline legs")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's outputs (solve transforms, a seeded sample of the fused volume) "
+                        "as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline legs")
     p.add_argument("--gn", action="append", default=[], metavar="KEY=VALUE", help=argparse.SUPPRESS)   # (A/B: GN params)
     p.add_argument("--no-prefetch", dest="prefetch", action="store_false",
                    help="set up each frame's solve inline instead of prefetching it during the previous frame")
@@ -96,6 +111,8 @@ def parse():
     p.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for "
                                                    "CPU launch checks and rehearsals with ranks sharing a device)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     if a.config is None:
         a.config = 5 if a.gpus > 1 and a.mode == "replicas" else 3
     cfg = dict(CONFIGS[a.config])
@@ -200,8 +217,6 @@ def main():
     torch.cuda.synchronize()
     pipe.integrate_source(frames[0])
     cache = pipe.wf.skin_tsdf_cache()
-    K = cache.k
-    n_skin_valid = int((cache.anchors.view(-1, 4)[:, K - 1] != -1).sum().item()) if cache.n_list else 0
     torch.cuda.synchronize()
     allreduce = sharded and a.solve == "allreduce"
     ar_events = []
@@ -276,25 +291,29 @@ def main():
     U = float(np.mean([int(u.item()) for u in upd]))
     kint_ms, kint_n = pipe.vol.integrate_timing(False)
     t_kint_loop = kint_ms * 1e-3 / max(1, kint_n)
-    # The same launch in isolation (after the timed region, untimed for `value`): in the frame loop the
-    # integrate shares the GPU with the next frame's prefetched solver setup, so its in-loop
-    # duration is not the kernel's own. Re-integrating the last frame into a scratch copy of the volume runs
-    # the identical work (same listed bricks, skins, depth: the update set does not depend on old values).
     vol = pipe.vol
-    keep = (vol.tsdf_b, vol.weight_b, vol.color_b)
-    vol.tsdf_b, vol.weight_b, vol.color_b = (x.clone() for x in keep)
-    torch.cuda.synchronize()
-    vol.integrate_timing(True)
-    # on a stream of its own: a launch on the legacy null stream waits for every other blocking stream the frame loop
-    # created (solve, integrate, prefetch slots), and those cross-stream waits landed between the three kernels the
-    # events bracket (140-150 us per launch instead of the kernels' 80)
-    with torch.cuda.stream(torch.cuda.Stream(dev)):
-        for _ in range(20):
-            vol.integrate_device(count_updates=True)
-    torch.cuda.synchronize()
-    kiso_ms, kiso_n = vol.integrate_timing(False)
-    vol.tsdf_b, vol.weight_b, vol.color_b = keep
-    t_kint = kiso_ms * 1e-3 / max(1, kiso_n)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, marks[-1][3], vol, "" if world == 1 else f"_rank{rank}")
+    t_kint = None
+    if a.full:
+        # The same launch in isolation (after the timed region, untimed for `value`): in the frame loop the
+        # integrate shares the GPU with the next frame's prefetched solver setup, so its in-loop
+        # duration is not the kernel's own. Re-integrating the last frame into a scratch copy of the volume runs
+        # the identical work (same listed bricks, skins, depth: the update set does not depend on old values).
+        keep = (vol.tsdf_b, vol.weight_b, vol.color_b)
+        vol.tsdf_b, vol.weight_b, vol.color_b = (x.clone() for x in keep)
+        torch.cuda.synchronize()
+        vol.integrate_timing(True)
+        # on a stream of its own: a launch on the legacy null stream waits for every other blocking stream the frame
+        # loop created (solve, integrate, prefetch slots), and those cross-stream waits landed between the three
+        # kernels the events bracket (140-150 us per launch instead of the kernels' 80)
+        with torch.cuda.stream(torch.cuda.Stream(dev)):
+            for _ in range(20):
+                vol.integrate_device(count_updates=True)
+        torch.cuda.synchronize()
+        kiso_ms, kiso_n = vol.integrate_timing(False)
+        vol.tsdf_b, vol.weight_b, vol.color_b = keep
+        t_kint = kiso_ms * 1e-3 / max(1, kiso_n)
     t_ar = (sum(x.elapsed_time(y) for x, y in ar_events) * 1e-3 / a.steps) if ar_events else 0.0
     mine = {"rank": rank, "device": local, "scene_seed": scene_seed, "nodes": int(seq.nodes.shape[0]),
             "ms_per_frame": 1e3 * elapsed / a.steps,
@@ -308,27 +327,6 @@ def main():
 
     frames_done = a.steps * (world if a.mode == "replicas" else 1)
     value = frames_done / elapsed_max
-    # algorithmic bytes of one integrate launch: palette-rank anchors 4 B per voxel
-    # of every listed brick + the brick's palette (64 x u16 + count); weights 16 B + tsdf/weight 8 B read
-    # per skin-valid voxel; per updated voxel tsdf/weight write 8 B + colour read+write 8 B. Node records
-    # and the depth/colour images are L2-resident and not counted.
-    B_listed = cache.n_list * (512 * 4 + 132) + n_skin_valid * 24 + U * 16
-    # with the brick cull (ofx_integrate_palette_cull, the default): the bricks it keeps move those bytes, every listed
-    # brick its palette count + ids (132 B) and flag (1 B) through the cull, and the depth image is read once for the
-    # tile maxima; the timed span covers the three kernels
-    act = getattr(vol, "_cull", None) if getattr(vol, "brick_cull", False) else None
-    if act is not None and cache.n_list:
-        live = act[1][:cache.n_list].to(torch.bool)
-        sv_slot = (cache.anchors.view(cache.n_list, 512, 4)[:, :, K - 1] != -1).sum(1)
-        n_live, sv_live = int(live.sum().item()), int(sv_slot[live].sum().item())
-        H_, W_ = (int(v) for v in vol.depth_t.shape)
-        B = n_live * (512 * 4 + 132) + cache.n_list * 133 + H_ * W_ * 4 + sv_live * 24 + U * 16
-    else:
-        n_live, sv_live, B = cache.n_list, n_skin_valid, B_listed
-    achieved = B / t_kint
-    # SURVEY §8(d)'s per-unit figure over the voxels this launch processes (every voxel of a listed brick):
-    # 32 B skin + 8 B tsdf/weight read per voxel, 8 B tsdf/weight write per updated voxel (colour separately)
-    B_survey = cache.n_list * 512 * 40 + U * 8
     # k_pcg_iter algorithmic (unique) bytes per PCG iteration: per JᵀJ block its 6x6 f64 values (288 B) + its
     # (col, slot) wave-list entry (8 B); per PCG row (nodes in cluster order, padded) the cluster-inverse
     # rows (6 x 48 f32 = 1152 B), the 8-vector state read + written (2 x 384 B), m read (48 B; the
@@ -400,25 +398,10 @@ def main():
                              "kernel-boundary floor + two dependent memory trips + the wave's instruction stream "
                              "(DESIGN.md §5); the 11-12 MB working set is L2/MALL-resident across launches. frac = "
                              "bytes_per_launch / avg_launch_us / peak"},
-        "roofline_integrate": {"kernel": "k_tile_max + k_brick_cull + k_integrate_pal4 (per-frame brick cull, then the "
-                                         "fused warp+integrate with an LDS node palette; VALU-bound: DESIGN.md "
-                                         "section 5)", "bound": "hbm",
-                               "achieved": achieved / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s",
-                               "frac": achieved / PEAK_HBM, "traffic": pmc_traffic("k_integrate_warp", workload, ("k_brick_cull", "k_tile_max")),
-                               "bytes_per_launch": B,
-                               "bytes_note": "this layout's minimal bytes for the bricks the per-frame cull keeps "
-                                             "(palette ranks, reads for skin-valid voxels only) + the cull's own reads; "
-                                             "frac_listed_bytes: the same per-unit bytes over every listed brick (the "
-                                             "work the launch covers); SURVEY 8(d)'s per-unit figure below",
-                               "cull_kept_bricks": n_live, "cull_kept_skin_valid_voxels": sv_live,
-                               "listed_bytes_per_launch": B_listed, "frac_listed_bytes": B_listed / t_kint / PEAK_HBM,
-                               "survey_bytes_per_launch": B_survey, "frac_survey_bytes": B_survey / t_kint / PEAK_HBM,
-                               "avg_launch_us": 1e6 * t_kint, "timing": "20 launches of the last frame in isolation "
-                               "(library hipEvents around each launch)", "in_loop_avg_launch_us": 1e6 * t_kint_loop,
-                               "listed_bricks": cache.n_list,
-                               "skin_valid_voxels": n_skin_valid, "updated_voxels": U},
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:   # the CPU baseline is an N=1 datapoint
+    if a.full:
+        res["roofline_integrate"] = integrate_roofline(cache, vol, U, t_kint, t_kint_loop, workload)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:   # the CPU baseline is an N=1 datapoint
         res["cpu_baseline"] = cpu_baseline(pipe, frames[total - 1], total - 1, a)
     if rank == 0:
         line = json.dumps(res)
@@ -429,6 +412,82 @@ def main():
     if dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 22   # voxels of the volume sample: 3 arrays x 4 B x 4 Mi = 48 MiB at the most
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, out, vol, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as <name>.npy under out_dir. The
+    solve's returned transforms and status, and the fused volume (TSDFVolume.get_volume_device: tsdf, color, weight)
+    at the same DUMP_SAMPLE seeded voxel indices every run (sorted, drawn with replacement from the flattened C-order
+    volume); a volume with no more voxels than that is written whole, flattened."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, x):
+        x = x.detach().cpu().numpy()
+        x = x.astype(np.float64 if x.dtype in (np.float64, np.int64) else np.float32, copy=False)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(x))
+
+    save("node_rotations", out["node_rotations"])
+    save("node_translations", out["node_translations"])
+    save("solve_status", out["_status"])
+    dense = vol.get_volume_device()
+    V = dense[0].numel()
+    idx = None
+    if V > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, V, size=DUMP_SAMPLE, dtype=np.int64))
+        idx = torch.from_numpy(idx).to(dense[0].device)
+    for name, x in zip(("tsdf", "color", "weight"), dense):
+        x = x.reshape(-1)
+        save(f"{name}_sample", x if idx is None else x[idx])
+
+
+def integrate_roofline(cache, vol, U, t_kint, t_kint_loop, workload):
+    """--full: the roofline of one warped integrate launch from its isolated timing t_kint (s per launch)."""
+    K = cache.k
+    n_skin_valid = int((cache.anchors.view(-1, 4)[:, K - 1] != -1).sum().item()) if cache.n_list else 0
+    # algorithmic bytes of one integrate launch (DESIGN.md §5): palette-rank anchors 4 B per voxel
+    # of every listed brick + the brick's palette (64 x u16 + count); weights 16 B + tsdf/weight 8 B read
+    # per skin-valid voxel; per updated voxel tsdf/weight write 8 B + colour read+write 8 B. Node records
+    # and the depth/colour images are L2-resident and not counted (SURVEY §8(d)).
+    B_listed = cache.n_list * (512 * 4 + 132) + n_skin_valid * 24 + U * 16
+    # with the brick cull (ofx_integrate_palette_cull, the default): the bricks it keeps move those bytes, every listed
+    # brick its palette count + ids (132 B) and flag (1 B) through the cull, and the depth image is read once for the
+    # tile maxima; the timed span covers the three kernels
+    act = getattr(vol, "_cull", None) if getattr(vol, "brick_cull", False) else None
+    if act is not None and cache.n_list:
+        live = act[1][:cache.n_list].to(torch.bool)
+        sv_slot = (cache.anchors.view(cache.n_list, 512, 4)[:, :, K - 1] != -1).sum(1)
+        n_live, sv_live = int(live.sum().item()), int(sv_slot[live].sum().item())
+        H_, W_ = (int(v) for v in vol.depth_t.shape)
+        B = n_live * (512 * 4 + 132) + cache.n_list * 133 + H_ * W_ * 4 + sv_live * 24 + U * 16
+    else:
+        n_live, sv_live, B = cache.n_list, n_skin_valid, B_listed
+    achieved = B / t_kint
+    # SURVEY §8(d)'s per-unit figure over the voxels this launch processes (every voxel of a listed brick):
+    # 32 B skin + 8 B tsdf/weight read per voxel, 8 B tsdf/weight write per updated voxel (colour separately)
+    B_survey = cache.n_list * 512 * 40 + U * 8
+    return {"kernel": "k_tile_max + k_brick_cull + k_integrate_pal4 (per-frame brick cull, then the "
+                      "fused warp+integrate with an LDS node palette; VALU-bound: DESIGN.md "
+                      "section 5)", "bound": "hbm",
+            "achieved": achieved / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s",
+            "frac": achieved / PEAK_HBM,
+            "traffic": pmc_traffic("k_integrate_warp", workload, ("k_brick_cull", "k_tile_max")),
+            "bytes_per_launch": B,
+            "bytes_note": "this layout's minimal bytes for the bricks the per-frame cull keeps "
+                          "(palette ranks, reads for skin-valid voxels only) + the cull's own reads; "
+                          "frac_listed_bytes: the same per-unit bytes over every listed brick (the "
+                          "work the launch covers); SURVEY 8(d)'s per-unit figure below",
+            "cull_kept_bricks": n_live, "cull_kept_skin_valid_voxels": sv_live,
+            "listed_bytes_per_launch": B_listed, "frac_listed_bytes": B_listed / t_kint / PEAK_HBM,
+            "survey_bytes_per_launch": B_survey, "frac_survey_bytes": B_survey / t_kint / PEAK_HBM,
+            "avg_launch_us": 1e6 * t_kint, "timing": "20 launches of the last frame in isolation "
+            "(library hipEvents around each launch)", "in_loop_avg_launch_us": 1e6 * t_kint_loop,
+            "listed_bricks": cache.n_list,
+            "skin_valid_voxels": n_skin_valid, "updated_voxels": U}
 
 
 def moose_bench(a):
