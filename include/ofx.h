@@ -363,6 +363,16 @@ int ofx_reduce_graph(const uint8_t* valid_nodes_mask, int32_t n_nodes, int32_t m
                      const int32_t* clusters, float* nodes_out, int32_t* edges_out, float* weights_out,
                      float* distances_out, int32_t* clusters_out, int32_t* n_kept, ofx_stream_t s);
 
+/* ---------------- Dense SPD solve (the exact Gauss-Newton step of small graphs) ----------------
+ * A x = b in f64 by a right-looking blocked Cholesky (LinearSolverLU's role, model/model.py:59-86). A is n x n, row-major
+ * with stride lda >= n; only its lower triangle is read, and it is overwritten by the factor L (A = L Lᵀ; the strict upper
+ * triangle is left as given). b (n) is overwritten by x. status (device int32[2]) = [1 if a pivot was <= 0 or not finite
+ * (A is not positive definite), index of the first such pivot]; x is all zeros then. Stream-ordered: no host sync, no
+ * allocation. One launch per 64-column panel step (panels + 2 in all) and one per panel of the backward solve; the only
+ * dependencies between workgroups are the launch boundaries, every sum runs in a fixed order (two runs are bit-identical). 1 <= n <= 3072, else
+ * OFX_ERR_RANGE. */
+int ofx_spd_solve(double* A, int32_t n, int32_t lda, double* b, int32_t* status, ofx_stream_t s);
+
 /* ---------------- Gauss-Newton (DeformNet.optimize) ---------------- */
 typedef struct ofx_gn_params {
   int32_t num_iter;          /* 10 (model.py:91) */
@@ -403,10 +413,17 @@ typedef struct ofx_gn_params {
                                 inversion cost (config 2's 1020 nodes: 464.7 vs 419.2 frames/s; config 3's 1998:
                                 292 vs 378; config 4's 4016: 106.5 vs 159.9). The Schwarz form needs the wave-list PCG
                                 (every 8-row wave <= 128 blocks, rows <= 20 blocks) and falls back to the cluster
-                                blocks otherwise */
+                                blocks otherwise. OFX_PRECOND_DIRECT (3) selects the linear solver itself, not a
+                                preconditioner: every GN step is solved exactly by a dense f64 Cholesky (ofx_spd_solve's
+                                launches) — no PCG, no stop rule, no host synchronisation inside the solve; pcg_* and
+                                precond_* are ignored, pcg_iterations and pcg_capped_steps read 0. It serves
+                                OFX_GN_OPTIMIZE on graphs of at most 512 nodes (3072 unknowns, a 75 MB dense buffer
+                                allocated at first use and kept on the handle); a larger graph is OFX_ERR_RANGE at
+                                setup, never a fallback to an estimated solve. OFX_GN_ARAP keeps the cluster PCG
+                                (ofx_gn_solver_info tells which ran). OFX_PRECOND_AUTO never picks it */
   int32_t _pad1;
 } ofx_gn_params;
-enum { OFX_PRECOND_CLUSTER = 0, OFX_PRECOND_SCHWARZ = 1, OFX_PRECOND_AUTO = 2 };
+enum { OFX_PRECOND_CLUSTER = 0, OFX_PRECOND_SCHWARZ = 1, OFX_PRECOND_AUTO = 2, OFX_PRECOND_DIRECT = 3 };
 
 /* OFX_GN_ARAP restates DeformNet.arap (model/model.py:1639-1986), the graph-update solve for nodes
  * that are invisible or new: no match rows (n_matches = 0); node_conf = valid-node mask (1/0) and
@@ -451,7 +468,8 @@ int ofx_gn_create(int32_t max_nodes, int32_t max_matches, void** handle);
 /* Profiling hook: returns (and resets) the device time of the PCG iteration loops recorded since the
  * last call (hipEvents on the solve stream; synchronises on them), the number of PCG launches (k_pcg_iter
  * launches) and of timed solves; `enable` switches recording for the
- * following steps. */
+ * following steps. Under OFX_PRECOND_DIRECT: the device time and the launches of the dense solve (scatter, Cholesky
+ * panel steps, backward solve, solution write-back) in their place. */
 int ofx_gn_timing(void* handle, int32_t enable, double* pcg_ms, int64_t* iter_launches, int64_t* n_solves);
 /* info (host int64[5]) = [n_nodes, n_matches, JᵀJ block count (nnzb), residual terms, rows] of the last
  * setup; rows = nodes in preconditioner-cluster order padded to whole clusters of 8 (<= 2·n_nodes + 8) */
@@ -461,6 +479,11 @@ int ofx_gn_info(void* handle, int64_t* info);
  * segment row, kernel launches per PCG iteration (ABI 5: 1 = the one-launch Schwarz iteration k_as_iter, 2 = k_pcg_iter
  * + k_as_apply; 1 for the cluster blocks)]. */
 int ofx_gn_precond_info(void* handle, int64_t* info);
+/* The linear solver of the last setup: info[4] = [direct active (OFX_PRECOND_DIRECT serving this problem), unknowns
+ * n = 6·n_nodes, panel width of the dense Cholesky (0 under the PCG), kernel launches per GN step of the direct path
+ * (scatter, the Cholesky panel steps, the backward solve, solution write-back and the GN update; 0 under the PCG)].
+ * No synchronisation. */
+int ofx_gn_solver_info(void* handle, int64_t* info);
 /* Waves per PCG cluster workgroup of k_pcg_iter for the last setup (before any: for a small problem): 2 up to
  * 384 clusters (default) or 1 (environment OFX_PCG_W1 set to anything but "" / "0" at create; tuning and A/B
  * only); larger problems always run one wave per cluster. */

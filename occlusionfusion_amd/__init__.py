@@ -8,7 +8,7 @@ ImportError if it is missing. (`synthetic` and `build` are plain-Python helpers 
 _EXPORTS = {
     "TSDFVolume": "tsdf", "volume_geometry": "tsdf", "shard_bricks": "sharding", "match_range": "sharding",
     "WarpField": "warpfield", "EDGraph": "warpfield",
-    "GaussNewtonSolver": "registration", "Registration": "registration",
+    "GaussNewtonSolver": "registration", "Registration": "registration", "spd_solve": "registration",
     "FusionPipeline": "pipeline",
     "backproject_depth": "image_proc", "compute_mesh_from_depth": "image_proc", "depth_2_pc": "image_proc",
 }

@@ -99,11 +99,13 @@ _SIGS = {
     "ofx_node_edge_cleanup": [P, c_int32, c_int32, P, P, P],
     "ofx_compute_clusters": [P, c_int32, c_int32, P, P, P, P],
     "ofx_reduce_graph": [P, c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P, P],
+    "ofx_spd_solve": [P, c_int32, c_int32, P, P, P],
     "ofx_gn_create": [c_int32, c_int32, P],
     "ofx_gn_destroy": [P],
     "ofx_gn_timing": [P, c_int32, P, P, P],
     "ofx_gn_info": [P, P],
     "ofx_gn_precond_info": [P, P],
+    "ofx_gn_solver_info": [P, P],
     "ofx_gn_pcg_waves": [P, P],
     "ofx_gn_step_fused": [P, P],
     "ofx_gn_stopped": [P, P],

@@ -63,6 +63,7 @@ constexpr int kProj = OFX_KPROJ;   // warm start: Galerkin projection on the las
 constexpr int kProjP = kProj * (kProj + 1) / 2 + kProj;   // projection partial streams (Gram upper triangle + Xᵀb)
 constexpr int kCS = 8;        // nodes per preconditioner cluster (= PCG rows per wave)
 constexpr int kMaxNodes = 8192;   // dense slot map of (2·max_nodes + kCS)² entries
+constexpr int kDirectMaxNodes = 512;   // OFX_PRECOND_DIRECT: 3072 unknowns, a 75 MB dense f64 buffer (ofx_spd_solve's limit)
 // Overlapping additive Schwarz (as_on): the ring of a cluster holds its kAsRing A-neighbours with the most coupling terms,
 // and a row joins at most kAsX rings, so an output cluster has at most kAsSrc contributing subdomains and kAsRS row
 // segments (a kAsD-entry inverse row each); kAsGat >= kAsSrc·kAsDN rounded up to whole passes of the apply's 192
@@ -265,7 +266,13 @@ struct Gn : GnDev {
   hipEvent_t ev_side = nullptr;
   int64_t pf_used = 0, pf_missed = 0;   // solves that used / discarded a prefetched setup
   int32_t ep_next = 1;
-  int as_env = -1;                  // OFX_PRECOND override of params.precond (-1: none)
+  int as_env = -1;                  // OFX_PRECOND override of params.precond (-1: none; 3: direct)
+  // exact dense solve (OFX_PRECOND_DIRECT, OFX_GN_OPTIMIZE): the dense lower triangle (dn_n x dn_n, row-major) and b / x
+  // of the 6·N_real unknowns in caller node order, allocated at the first setup that asks for it and kept
+  int direct = 0;                   // the last setup's solver: 1 = dense Cholesky instead of the PCG
+  int dn_n = 0, dn_cap = 0;
+  double *dn_A = nullptr, *dn_b = nullptr;
+  int32_t* dn_status = nullptr;     // ofx_spd_solve's status of the current GN step
   void (*idle_fn)(void*) = nullptr; // ofx_gn_set_idle_hook: host work run once at the next solve's first PCG wait
   void* idle_arg = nullptr;
   int as_lanes = 2;                 // k_as_apply's lanes per segment (OFX_AS_LANES)
@@ -4346,6 +4353,56 @@ __global__ __launch_bounds__(256) void k_step(GnDev g, const double* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------- exact dense solve (OFX_PRECOND_DIRECT)
+// The assembled block-sparse A (already damped by this step's λ_k I) into the dense lower triangle D (n x n, n =
+// 6·N_real, caller node order: padding rows dropped through perm) and b beside it; what the pattern does not cover is
+// zeroed. One thread per node pair (a >= c) and block entry. Also clears the step's ofx_spd_solve status.
+__global__ __launch_bounds__(256) void k_dn_scatter(GnDev g, const double* __restrict__ A, const double* __restrict__ rhs,
+                                                    double* __restrict__ D, double* __restrict__ bv,
+                                                    int32_t* __restrict__ status) {
+  if (g.flags[F_STOPPED]) return;
+  const int Nr = g.N_real, n = 6 * Nr;
+  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e < 2) status[e] = 0;
+  if (e < n) bv[e] = rhs[6 * (int64_t)g.iperm[e / 6] + e % 6];
+  if (e >= 36 * (int64_t)Nr * Nr) return;
+  const int q = (int)(e % 36), c = (int)((e / 36) % Nr), a = (int)(e / 36 / Nr);
+  if (c > a) return;
+  const int r = q / 6, cc = q % 6;
+  if (c == a && cc > r) return;   // the strict upper triangle is never read
+  const int sl = g.map[(int64_t)g.iperm[a] * g.N + g.iperm[c]];
+  D[(int64_t)(6 * a + r) * n + 6 * c + cc] = sl > 0 ? A[36 * (int64_t)(sl - 1) + q] : 0.0;
+}
+
+// The dense solution back where k_step reads it (st[V_N·(6·row + c) + V_X]; 0 for padding rows) and what k_step reports:
+// F_DONE = 1 with 0 PCG iterations, |b|² (part_b, summed in a fixed order), F_ILL for a bad pivot. One workgroup.
+__global__ __launch_bounds__(1024) void k_dn_writeback(GnDev g, const double* __restrict__ x, const double* __restrict__ rhs,
+                                                       const int32_t* __restrict__ status) {
+  if (g.flags[F_STOPPED]) return;
+  __shared__ double s[1024];
+  const int tid = threadIdx.x;
+  const bool bad = status[0] != 0;
+  double bb = 0.0;
+  for (int64_t e = tid; e < 6 * (int64_t)g.N; e += 1024) {
+    const int p = g.perm[e / 6];
+    g.st[V_N * e + V_X] = (p >= 0 && !bad) ? x[6 * (int64_t)p + e % 6] : 0.0;
+    const double bq = p >= 0 ? rhs[e] : 0.0;
+    bb += bq * bq;
+  }
+  s[tid] = bb;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (tid < o) s[tid] += s[tid + o];
+    __syncthreads();
+  }
+  for (int i = tid; i < g.nwg_row; i += 1024) g.part_b[i] = i == 0 ? s[0] : 0.0;
+  if (tid == 0) {
+    g.flags[F_DONE] = 1;
+    g.flags[F_PCG_IT] = 0;
+    if (bad) g.flags[F_ILL] = 1;
+  }
+}
+
 // arap mode, lambda_flow = 0: remove each connected component's mean translation from the PCG
 // solution (one wave per component, fixed-order sums). A·n = λ_LM·n for that common translation n and
 // b ⊥ n, so the dense LU solution has no n component; CG barely resolves the λ_LM eigenvalue.
@@ -4404,7 +4461,8 @@ static void free_all(Gn* g) {
                   g->part_p, g->part_b, g->part_loss,
                   g->loss_log, g->stat, g->step_state, g->xh, g->th, g->step_args, g->d_gnodes, g->d_gedges, g->d_gdiff, g->perm, g->iperm, g->comp_rows, g->comp_off,
                   g->up_of, g->up_slot, g->up_tr, g->as_cand, g->as_csc, g->as_acc, g->as_dom, g->as_meta, g->as_gat,
-                  g->as_dst, g->as_slab, g->as_w, g->as_src, g->as_dsc, g->as_rsc, g->as_tab, g->as_mem, g->as_memn};
+                  g->as_dst, g->as_slab, g->as_w, g->as_src, g->as_dsc, g->as_rsc, g->as_tab, g->as_mem, g->as_memn,
+                  g->dn_A, g->dn_b, g->dn_status};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (g->host_flags) (void)hipHostFree(g->host_flags);
@@ -4861,8 +4919,10 @@ int ofx_gn_create(int32_t max_nodes, int32_t max_matches, void** handle) {
   {   // tuning / A-B: OFX_PCG_W1=1 (any value but "0" / empty) selects one wave per cluster
     const char* e = getenv("OFX_PCG_W1");
     g->pcg_w2 = (e && e[0] && strcmp(e, "0") != 0) ? 0 : 1;
-    const char* pe = getenv("OFX_PRECOND");   // A/B override of params.precond: "as" = Schwarz, "bj" = cluster blocks
-    g->as_env = (pe && strcmp(pe, "as") == 0) ? 1 : (pe && strcmp(pe, "bj") == 0) ? 0 : -1;
+    // A/B override of params.precond: "as" = Schwarz, "bj" = cluster blocks, "direct" = the exact dense solve
+    const char* pe = getenv("OFX_PRECOND");
+    g->as_env = (pe && strcmp(pe, "as") == 0) ? 1 : (pe && strcmp(pe, "bj") == 0) ? 0
+              : (pe && strcmp(pe, "direct") == 0) ? OFX_PRECOND_DIRECT : -1;
     // lanes per Schwarz segment in k_as_apply (OFX_AS_LANES=1|2|4, A/B): 2 (16-row rings: 410 / 432 / 412 against
     // 387 / 390 / 372 frames/s with one, one box; with 12-row rings one and two were within noise)
     const char* le = getenv("OFX_AS_LANES");
@@ -4980,6 +5040,18 @@ int ofx_gn_precond_info(void* handle, int64_t* info) {
     for (int l = 0; l < kAsDN; ++l) drows += dom[(size_t)c * kAsDN + l] >= 0 ? 1 : 0;
   }
   info[1] = ncl; info[2] = segs; info[3] = srcs; info[4] = rows; info[5] = drows;
+  return OFX_OK;
+}
+
+int ofx_gn_solver_info(void* handle, int64_t* info) {
+  Gn* g = (Gn*)handle;
+  if (g) prep_wait(g);
+  OFX_CHECK_ARG(g && info, "null handle/info");
+  info[0] = g->direct;
+  info[1] = 6 * (int64_t)g->N_real;
+  info[2] = g->direct ? dense_panel_width() : 0;
+  // scatter + the Cholesky launches + solution write-back + k_step (the linearisation's two launches not counted)
+  info[3] = g->direct ? 3 + dense_spd_launches(g->dn_n) : 0;
   return OFX_OK;
 }
 
@@ -5214,10 +5286,19 @@ static int gn_setup(Gn* g, const ofx_gn_problem* pb, const ofx_gn_params* prm, i
   OFX_CHECK_ARG(prm->num_iter >= 0 && prm->num_iter <= 64, "num_iter must be in [0,64]");
   OFX_CHECK_ARG(prm->pcg_max_iter >= 1, "pcg_max_iter must be >= 1");
   OFX_CHECK_ARG(prm->precond_rot_tol >= 0.0, "precond_rot_tol must be >= 0");
-  OFX_CHECK_ARG(prm->precond == OFX_PRECOND_CLUSTER || prm->precond == OFX_PRECOND_SCHWARZ || prm->precond == OFX_PRECOND_AUTO,
-                "bad precond %d", prm->precond);
+  OFX_CHECK_ARG(prm->precond == OFX_PRECOND_CLUSTER || prm->precond == OFX_PRECOND_SCHWARZ ||
+                prm->precond == OFX_PRECOND_AUTO || prm->precond == OFX_PRECOND_DIRECT, "bad precond %d", prm->precond);
   hipStream_t hs = as_stream(s);
   int N0 = pb->n_nodes, M = pb->n_matches, NB = pb->n_neighbors;
+  // the exact dense solve (OFX_PRECOND_DIRECT, or OFX_PRECOND=direct) serves DeformNet.optimize; arap keeps the cluster
+  // PCG. A graph past its limit is an error, never an estimated solve in place of the exact one that was asked for.
+  const bool direct_req = (g->as_env >= 0 ? g->as_env == OFX_PRECOND_DIRECT : prm->precond == OFX_PRECOND_DIRECT) &&
+                          prm->mode == OFX_GN_OPTIMIZE;
+  if (direct_req && N0 > kDirectMaxNodes) {
+    set_error("precond=direct serves graphs of at most %d nodes (%d unknowns); n_nodes = %d", kDirectMaxNodes,
+              6 * kDirectMaxNodes, N0);
+    return OFX_ERR_RANGE;
+  }
   if ((int64_t)N0 * NB > 0) OFX_CHECK_ARG(pb->edges, "null edges");
   // row order (cluster preconditioner): rebuilt when the graph differs from the previous solve's. If a
   // row order exists for a graph of the same size, assume it still holds and compare on the device; the
@@ -5406,7 +5487,8 @@ static int gn_setup(Gn* g, const ofx_gn_problem* pb, const ofx_gn_params* prm, i
   }
   g->nnzb = nnz;
   hipLaunchKernelGGL(k_row_assign, dim3(N), dim3(256), 0, hs, N, g->map, g->row_ptr, g->col, g->blk_row);
-  hipLaunchKernelGGL(k_wave_list, dim3(grid_for((int64_t)(N / kCS) * kWL, 256, 1 << 30)), dim3(256), 0, hs, *g);
+  if (!direct_req)   // (the PCG's per-wave block lists: the direct solve reads A through the slot map)
+    hipLaunchKernelGGL(k_wave_list, dim3(grid_for((int64_t)(N / kCS) * kWL, 256, 1 << 30)), dim3(256), 0, hs, *g);
   g->pat_N = N;
   g->pat_nnzb = nnz;
   // upper blocks: slot -> u by a scan of the flags (blk_cnt as scratch), u -> slot and transpose
@@ -5434,9 +5516,24 @@ static int gn_setup(Gn* g, const ofx_gn_problem* pb, const ofx_gn_params* prm, i
   // Schwarz tables (blk_off still holds the per-block term counts' offsets)
   g->as_on = 0;
   constexpr int kAsAutoNodes = 1536;   // OFX_PRECOND_AUTO: Schwarz from this graph size on (ofx.h)
-  const bool as_req = g->as_env >= 0 ? g->as_env == 1
-                                     : (g->prm.precond == OFX_PRECOND_SCHWARZ ||
-                                        (g->prm.precond == OFX_PRECOND_AUTO && g->N_real >= kAsAutoNodes));
+  const bool as_req = !direct_req &&
+                      (g->as_env >= 0 ? g->as_env == 1
+                                      : (g->prm.precond == OFX_PRECOND_SCHWARZ ||
+                                         (g->prm.precond == OFX_PRECOND_AUTO && g->N_real >= kAsAutoNodes)));
+  g->direct = direct_req ? 1 : 0;
+  if (direct_req) {   // the dense buffers, allocated at first use and kept on the handle
+    const int n = 6 * N0;
+    if (n > g->dn_cap) {
+      for (auto pp : {(void**)&g->dn_A, (void**)&g->dn_b})
+        if (*pp) { OFX_HIP(hipFree(*pp)); *pp = nullptr; }
+      g->dn_cap = 0;
+      OFX_HIP(hipMalloc((void**)&g->dn_A, (size_t)n * n * sizeof(double)));
+      OFX_HIP(hipMalloc((void**)&g->dn_b, (size_t)n * sizeof(double)));
+      g->dn_cap = n;
+    }
+    if (!g->dn_status) OFX_HIP(hipMalloc((void**)&g->dn_status, 2 * sizeof(int32_t)));
+    g->dn_n = n;
+  }
   if (as_req && g->max_wave <= kWL && g->max_deg <= kRowMax) {   // (the Schwarz form needs the wave-list PCG)
     const int ncl = N / kCS;
     if (ncl > g->as_cap) {
@@ -5564,6 +5661,50 @@ int ofx_gn_step(void* handle, int32_t gn_iter, double* A, double* rhs, ofx_strea
   hipStream_t hs = as_stream(s);
   const int fs = fence_side(g, hs);
   if (fs) return fs;
+  if (g->direct) {
+    // the exact dense solve: scatter, the Cholesky panel launches, the solution back into the PCG state's x, then the
+    // usual k_step. Nothing here waits for the device: every launch returns at once after a stop.
+    g->ep = g->ep_next++;   // (k_step stores it as the host-visible stop word)
+    g->gn_iter_now = gn_iter;
+    g->step_fused = false;
+    const int n = g->dn_n;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (g->timing) {   // (ofx_gn_timing: the linear solve's device time and launches, as the PCG loop's under the PCG)
+      OFX_HIP(hipEventCreate(&e0));
+      if (hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, hs) != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        set_error("direct solve: timing events");
+        return OFX_ERR_HIP;
+      }
+    }
+    hipLaunchKernelGGL(k_dn_scatter, dim3(grid_for(36 * (int64_t)g->N_real * g->N_real, 256, 1 << 30)), dim3(256), 0, hs,
+                       *g, (const double*)A, (const double*)rhs, g->dn_A, g->dn_b, g->dn_status);
+    const int ds = dense_spd_enqueue(g->dn_A, n, n, g->dn_b, g->dn_status, g->flags + F_STOPPED, hs);
+    if (ds) {
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+      return ds;
+    }
+    hipLaunchKernelGGL(k_dn_writeback, dim3(1), dim3(1024), 0, hs, *g, (const double*)g->dn_b, (const double*)rhs,
+                       (const int32_t*)g->dn_status);
+    if (g->timing) {   // (owned by g->ev from here: ofx_gn_timing destroys them)
+      g->ev.emplace_back(e0, e1);
+      g->n_iter_launches += 2 + dense_spd_launches(n);
+      OFX_HIP(hipEventRecord(e1, hs));
+    }
+    hipLaunchKernelGGL(k_step, dim3(grid_for(g->N, 256)), dim3(256), 0, hs, *g, (const double*)rhs, 64,
+                       g->prm.pcg_max_iter, gn_iter, (double*)nullptr);
+    OFX_LAUNCH_CHECK();
+    if (g->idle_fn) {   // (ofx_gn_set_idle_hook: no PCG wait exists here; once the first step's launches are queued)
+      void (*fn)(void*) = g->idle_fn;
+      void* arg = g->idle_arg;
+      g->idle_fn = nullptr;
+      g->idle_arg = nullptr;
+      fn(arg);
+    }
+    return OFX_OK;
+  }
   int st = gn_pcg(g, gn_iter, A, rhs, hs);
   if (st) return st;
   if (g->step_fused) return OFX_OK;   // the converging PCG launch took the step (fused_step)

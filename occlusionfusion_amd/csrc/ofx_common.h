@@ -74,6 +74,12 @@ __device__ __forceinline__ float vox2world(float o, double vs, int i) {
 
 inline hipStream_t as_stream(ofx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// dense.hip: the launches of ofx_spd_solve on hs (status must be zero when they run; stop, nullable: a device word that
+// makes every launch return at once when set), their number for n unknowns, and the panel width
+int dense_spd_enqueue(double* A, int n, int lda, double* b, int32_t* status, const int32_t* stop, hipStream_t hs);
+int dense_spd_launches(int n);
+int dense_panel_width();
+
 inline unsigned grid_for(int64_t n, int block, int64_t cap = 1 << 20) {
   int64_t g = (n + block - 1) / block;
   if (g > cap) g = cap;

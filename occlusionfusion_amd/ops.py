@@ -189,6 +189,34 @@ def _(points, anchors, weights, valid, packed_nodes, normals):
     return torch.empty_like(points)
 
 
+# --------------------------------------------------------------------------------------------- dense SPD solve
+@_op("spd_solve", mutates_args=())
+def spd_solve(A: Tensor, b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """ofx_spd_solve on copies: A (n,n) f64 symmetric positive definite (only its lower triangle is read; a row stride
+    >= n is passed on as lda), b (n) f64 -> (L (n,n): the Cholesky factor in the lower triangle, the strict upper triangle
+    as given; x (n) = A⁻¹b; status int32[2] = [not positive definite / non-finite pivot, index of the first bad pivot],
+    x = 0 then)."""
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or b.dim() != 1 or b.shape[0] != A.shape[0]:
+        raise ValueError(f"spd_solve: A must be (n, n) and b (n); got {tuple(A.shape)}, {tuple(b.shape)}")
+    if A.dtype != torch.float64 or b.dtype != torch.float64:
+        raise ValueError("spd_solve: A and b must be float64")
+    n = A.shape[0]
+    lda = max(A.stride(0) if ((A.stride(1) == 1 or n == 1) and A.stride(0) >= n) else n, 1)
+    buf = torch.empty((n, lda), dtype=torch.float64, device=A.device)
+    L = buf[:, :n]
+    L.copy_(A)
+    x = b.clone().contiguous()
+    status = torch.empty(2, dtype=torch.int32, device=A.device)
+    call("ofx_spd_solve", ptr(buf), n, lda, ptr(x), ptr(status), _stream(A))
+    return L.contiguous(), x, status
+
+
+@spd_solve.register_fake
+def _(A, b):
+    n = A.shape[0]
+    return (A.new_empty((n, n)), b.new_empty((n,)), A.new_empty((2,), dtype=torch.int32))
+
+
 # --------------------------------------------------------------------------------------------- Gauss-Newton
 def _gn_problem(nodes, edges, edge_weights, tpos, conf, src, anchors, weights, tgt, target_px, target_py, prev_rot,
                 prev_trans, intr):
@@ -206,7 +234,8 @@ def _gn_problem(nodes, edges, edge_weights, tpos, conf, src, anchors, weights, t
 def _gn_params(fparams, iparams):
     """fparams = [lambda_flow, lambda_depth, lambda_arap, lambda_motion, lm_factor, stop_loss_diff, pcg_tol,
     pcg_err_tol, precond_rot_tol]; iparams = [num_iter, use_edge_weighting, pcg_max_iter, pcg_warm, mode,
-    precond_every(, precond: OFX_PRECOND_CLUSTER 0 / OFX_PRECOND_SCHWARZ 1, default 0)]."""
+    precond_every(, precond: OFX_PRECOND_CLUSTER 0 / OFX_PRECOND_SCHWARZ 1 / OFX_PRECOND_AUTO 2 / OFX_PRECOND_DIRECT 3,
+    default 0)]."""
     p = _lib.GnParams()
     (p.lambda_flow, p.lambda_depth, p.lambda_arap, p.lambda_motion, p.lm_factor, p.stop_loss_diff,
      p.pcg_tol, p.pcg_err_tol, p.precond_rot_tol) = (float(v) for v in fparams)
@@ -340,4 +369,4 @@ def _(state, handle, n_nodes, num_iter):
 
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
-       "gn_linearize", "gn_step", "gn_finish")
+       "gn_linearize", "gn_step", "gn_finish", "spd_solve")

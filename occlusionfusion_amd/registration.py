@@ -28,8 +28,11 @@ GN_DEFAULTS = dict(num_iter=10, lambda_flow=0.0, lambda_depth=1.0, lambda_arap=0
                    lm_factor=1e-7, stop_loss_diff=1.0, use_edge_weighting=False, pcg_max_iter=2000, pcg_tol=2e-6,
                    pcg_warm=True, precond_every=10, pcg_err_tol=2e-6, precond_rot_tol=0.3, precond="auto")
 # PCG preconditioner (ofx_gn_params.precond): overlapping additive Schwarz, the 8-node cluster blocks, or
-# auto (Schwarz for graphs of >= 1536 nodes)
-_PRECOND = {"cluster": 0, "schwarz": 1, "auto": 2}
+# auto (Schwarz for graphs of >= 1536 nodes). precond="direct" is not a preconditioner but the linear solver itself:
+# every GN step solved exactly by a dense f64 Cholesky on the device (ofx_spd_solve), for graphs of <= 512 nodes — the
+# reference's own LU, no PCG and no stop rule (pcg_* / precond_* ignored, pcg_iterations = 0); a larger graph raises
+# OfxError. "auto" never picks it.
+_PRECOND = {"cluster": 0, "schwarz": 1, "auto": 2, "direct": 3}
 MAX_MATCHES_EVAL = 10000   # settings/custom_settings.py:36
 
 
@@ -164,6 +167,13 @@ class GaussNewtonSolver:
         call("ofx_gn_precond_info", self._h, arr)
         return dict(zip(("schwarz", "clusters", "segments", "sources", "gathered_rows", "subdomain_rows", "row_length",
                          "launches_per_iteration"), list(arr)))
+
+    def solver_info(self):
+        """The last setup's linear solver: dict(direct, unknowns, panel_width, launches_per_gn_step)
+        (ofx_gn_solver_info; direct = 1 when precond="direct" served the problem, 0 under the PCG)."""
+        arr = (ctypes.c_int64 * 4)()
+        call("ofx_gn_solver_info", self._h, arr)
+        return dict(zip(("direct", "unknowns", "panel_width", "launches_per_gn_step"), list(arr)))
 
     def stopped(self):
         """The solve's stop flag as the host sees it (ofx_gn_stopped: no synchronisation)."""
@@ -396,6 +406,16 @@ class GaussNewtonSolver:
                 break
         out = torch.ops.ofx.gn_finish(self._state, h, N, int(self.params["num_iter"]))
         return self._pack(out, sync)
+
+
+def spd_solve(A, b):
+    """Dense f64 solve A x = b of a symmetric positive definite A on the device (torch.ops.ofx.spd_solve, on copies):
+    -> (L, x, status). A (n,n) / b (n): CUDA float64 tensors or arrays (uploaded to the current device); only A's lower
+    triangle is read; 1 <= n <= 3072 (else OfxError). status = [not positive definite, first bad pivot]; x = 0 then."""
+    d = A.device if isinstance(A, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    At = A if isinstance(A, torch.Tensor) else torch.as_tensor(np.asarray(A, np.float64), device=d)
+    bt = b if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, np.float64), device=d)
+    return torch.ops.ofx.spd_solve(At, bt)
 
 
 def depth_2_pc_device(depth, intrin):
