@@ -207,7 +207,8 @@ static_assert(std::is_trivially_copyable<GnDev>::value, "kernel argument");
 //   dsc  [kAsD] f32   the inverse's scales d = √diag Z (k_as_invert)
 //   gh   [kAsRing·6] double2  ghost (w, z) of the ring rows (the owners' recurrences, repeated bit for bit)
 //   y    [2][cap][kAsD] f64  per parity the contributions y_c = D Ẑ D w[D_c]
-//   slab [kAsK][kAsD] uint4  Ẑ's rows (8 fp16 per word), word k of every row contiguous
+//   slab [kAsK][kAsD] uint4  Ẑ's rows (8 fp16 per word, its 32-bit pairs in the order 0, 2, 1, 3: a lane pair of the
+//                     contribution dot takes 8-B halves), word k of every row contiguous
 struct AsTabP {
   int2* blk; int4* con; int32_t* s2n; int32_t* row; float* dsc; double2* gh; double* y; uint4* slab;
 };
@@ -2090,7 +2091,8 @@ __device__ __forceinline__ void as_invert_body(const GnDev& g, const double* __r
     uint4* sl = as_tab_at(g.as_tab, g.as_tab_cap).slab + (int64_t)c * kAsK * kAsD;
     for (int i = t; i < n * kAsK; i += T) {
       const int k = i / n, R = i - k * n;
-      sl[(int64_t)k * kAsD + R] = reinterpret_cast<const uint4*>(s_z + R * kAsD)[k];
+      const uint4 v = reinterpret_cast<const uint4*>(s_z + R * kAsD)[k];
+      sl[(int64_t)k * kAsD + R] = make_uint4(v.x, v.z, v.y, v.w);
     }
   }
   if (t < kCS) g.racc[c * kCS + t] = 0.0;
@@ -2325,7 +2327,8 @@ __device__ __forceinline__ void as_invert_mfma(const GnDev& g, const double* __r
     uint4* sl = as_tab_at(g.as_tab, g.as_tab_cap).slab + (int64_t)c * kAsK * kAsD;
     for (int i = t; i < n * kAsK; i += kInvT) {
       const int k = i / n, R = i - k * n;
-      sl[(int64_t)k * kAsD + R] = reinterpret_cast<const uint4*>(s_z + R * kAsD)[k];
+      const uint4 v = reinterpret_cast<const uint4*>(s_z + R * kAsD)[k];
+      sl[(int64_t)k * kAsD + R] = make_uint4(v.x, v.z, v.y, v.w);
     }
   }
   if (t < kCS) g.racc[c * kCS + t] = 0.0;
@@ -3424,9 +3427,11 @@ __global__ __launch_bounds__(kW2 ? 128 : 64) __attribute__((amdgpu_waves_per_eu(
       }
     }
     OFX_STAMP(3)
-    if (kW2) {   // both waves' products: an LDS barrier (no memory release)
+    if (kW2) {   // both waves' products: an LDS barrier (no memory release; the clobbers pin the LDS accesses' side)
       __builtin_amdgcn_s_waitcnt(0xC07F);
+      asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
     } else {
       wave_lds_sync();
     }
@@ -3542,15 +3547,84 @@ __global__ __launch_bounds__(kW2 ? 128 : 64) __attribute__((amdgpu_waves_per_eu(
 // bitwise those of the two-launch form. One exchange per iteration: one kernel boundary.
 // Roles (1024 threads; the rows first in dispatch order): waves 0-2 the rows: 0 the own rows (k_pcg_iter's wave: scalars,
 // stop, recurrences, partials, the converging launch's GN step), 1-2 the ring rows (ghost z, w); waves 3-7 one S2 node each
-// (its contributions summed into m; a second pass past 320 nodes) and one inverse row half each (the dot product, as
-// k_as_apply's two lanes); waves 8-15 the blocks of D_c's rows (the A rows and the products). Trip 1: the stop word, tables, state,
-// partials, inverse rows; trip 2: the A blocks and the contributions. Three barriers (m, products, the w image).
+// (its contributions summed into m; a second pass past 320 nodes); waves 8-15 the blocks of D_c's rows (the A rows and the
+// products); waves 3-11 a quarter of an inverse row each (the contribution dot, as_dot_*: k_as_apply's chains over four
+// lanes). Trip 1: the stop word, tables, state, partials; trip 2: the A blocks and the contributions. Three barriers (m, products, the w image).
 // k_as_iter's workgroup barrier: LDS writes complete (lgkmcnt(0)), then s_barrier — no memory fence: __syncthreads()
 // would also wait for every outstanding global load and store of the wave (the A rows, the inverse rows, the state
-// stores), which the roles consume or retire later
+// stores), which the roles consume or retire later. Both intrinsics are memory-free to the compiler: the empty asm with
+// a memory clobber on either side of s_barrier keeps the LDS accesses (s_m, s_prod, s_w, s_leave, s_ab) on their side
+// of it by construction (no instruction)
 __device__ __forceinline__ void as_lds_barrier() {
   __builtin_amdgcn_s_waitcnt(0xC07F);
+  asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// The contribution dot y_c = D Ẑ (D w) over four lanes per inverse row (k_as_iter, k_as_w0: 4·kAsD lanes, waves 3-11).
+// k_as_apply's two lanes per segment run four accumulation chains a0..a3 over their half hl of the row's words; here
+// lane tq = 4·row + 2·hl + g runs the chains a(2g), a(2g + 1) of half hl in their order — every chain is the same
+// sequence of f64 FMAs — and the sums (a0 + a1) + (a2 + a3), then the two halves, are formed across the lane pairs by
+// DPP (IEEE addition commutes: the same bits in every lane of the quad). A lane loads only its 8-byte half of each word
+// (the slab's words are stored in the 32-bit order 0, 2, 1, 3: k_as_invert), 9 loads, and converts fp16 -> f64 ahead of
+// the last barrier, where it only waits.
+constexpr int kAsDotT = 4 * kAsD;   // lanes of the dot (576)
+constexpr int kDotBW = (kAsDotT - 5 * 64 + 63) / 64;   // block waves (from wave 8) that take the lanes past the S2 waves'
+static_assert(kDotBW >= 0 && kDotBW <= 8, "the dot's lanes fit waves 3-15");
+struct AsDotRow {
+  uint2 z[9];
+  float dsc;
+  int yd;   // the row's entry in a parity of y
+};
+static_assert(kAsK == 18, "the dot's lanes take 9 words of their half each");
+__device__ __forceinline__ void as_dot_load(const AsTabP& tp, int c, int tq, AsDotRow& d) {
+  const int ry = min(tq >> 2, kAsD - 1), hl = (tq >> 1) & 1, g = tq & 1;
+  const uint2* sl = reinterpret_cast<const uint2*>(tp.slab + ((int64_t)c * kAsK + 9 * hl) * kAsD + ry) + g;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) d.z[k] = sl[(int64_t)k * 2 * kAsD];
+  d.dsc = tp.dsc[(int64_t)c * kAsD + ry];
+  d.yd = c * kAsD + ry;   // (its entry in y)
+}
+__device__ __forceinline__ void as_dot_cvt(const AsDotRow& d, double (&f)[36]) {   // (fp16 -> f32 -> f64: exact)
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    f[4 * k] = (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(d.z[k].x & 0xFFFFu));
+    f[4 * k + 1] = (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(d.z[k].x >> 16));
+    f[4 * k + 2] = (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(d.z[k].y & 0xFFFFu));
+    f[4 * k + 3] = (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(d.z[k].y >> 16));
+  }
+}
+// (s_w: the w image; the quad's four lanes return the same bits)
+__device__ __forceinline__ double as_dot_sum(const double (&f)[36], const double* s_w, int tq) {
+  const int hl = (tq >> 1) & 1, g = tq & 1;
+  const double2* w2p = reinterpret_cast<const double2*>(s_w) + 36 * hl + g;
+  double a = 0.0, b = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const double2 p0 = w2p[4 * k], p2 = w2p[4 * k + 2];
+    a = fma(f[4 * k], p0.x, a);
+    b = fma(f[4 * k + 1], p0.y, b);
+    a = fma(f[4 * k + 2], p2.x, a);
+    b = fma(f[4 * k + 3], p2.y, b);
+  }
+  double dot = a + b;
+  dot += dpp_mov<0xB1>(dot);   // quad_perm [1, 0, 3, 2]: (a0 + a1) + (a2 + a3)
+  dot += dpp_mov<0x4E>(dot);   // quad_perm [2, 3, 0, 1]: the row's two halves
+  return dot;
+}
+// a dot lane from barrier 2 on (its inverse row loaded): the conversions while it waits for the w image, the dot, its
+// contribution into y (y_w: the parity written). leave (nullable): the converged iteration writes none
+__device__ __forceinline__ void as_dot_tail(const AsDotRow& d, const double* s_w, const int* leave, int tq, int nd,
+                                            double* y_w) {
+  as_lds_barrier();   // (2)
+  double f[36];
+  as_dot_cvt(d, f);
+#pragma unroll
+  for (int k = 0; k < 36; ++k) asm volatile("" : "+v"(f[k]));   // (the conversions stay on this side of the barrier)
+  as_lds_barrier();   // (3)
+  if (leave && *leave) return;
+  const double dot = as_dot_sum(f, s_w, tq);
+  if ((tq & 3) == 0 && tq < kAsDotT && (tq >> 2) < 6 * nd) y_w[d.yd] = (double)d.dsc * dot;
 }
 #ifdef OFX_STAMPS   // tuning build: per (iteration < 64, cluster) 8 clock stamps — 0 entry, 1 trip 1 landed, 2 scalars done,
                     // 3 after barrier 1, 4 after barrier 2, 5 after barrier 3 (own-row wave), 6 end; 7: the row sums done (after 4)
@@ -3588,7 +3662,7 @@ __global__ __launch_bounds__(kAsIterT) void k_as_iter(const int32_t* stopw, cons
   if (wave >= 8) {  // ---------------- blocks (waves 8-15; tb = block index)
     const int tb = t - kGB;
     int stop_ep = stopw[(int64_t)c * 64 + lane];
-    const int nb = rt[26];
+    const int nb = rt[26], nd = rt[25];
     typedef double gd2 __attribute__((ext_vector_type(2)));
     const __attribute__((address_space(1))) gd2* A2 =
         reinterpret_cast<const __attribute__((address_space(1))) gd2*>(reinterpret_cast<const uint64_t*>(scb)[kScAop]);
@@ -3602,6 +3676,9 @@ __global__ __launch_bounds__(kAsIterT) void k_as_iter(const int32_t* stopw, cons
       asm volatile("" ::: "memory");
       stop_ep = __builtin_amdgcn_readfirstlane(stop_ep);
       if (stop_ep != 0) return;
+      // all of trip 1 (one trip: it lands together) before the A rows: left to the compiler, each of the kP groups
+      // below waited for vmcnt(0) — its block entry, but also the group before it: kP dependent trips
+      __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
       double2 ar[kP][3];
 #pragma unroll
       for (int j = 0; j < kP; ++j)
@@ -3623,6 +3700,12 @@ __global__ __launch_bounds__(kAsIterT) void k_as_iter(const int32_t* stopw, cons
           const double2 b01 = ar[j][0], b23 = ar[j][1], b45 = ar[j][2];
           s_prod[pp] = fma(b45.y, x[5], fma(b45.x, x[4], fma(b23.y, x[3], fma(b23.x, x[2], fma(b01.y, x[1], b01.x * x[0])))));
         }
+      }
+      if (wave < 8 + kDotBW) {
+        AsDotRow dr;
+        as_dot_load(tp, c, t - 192, dr);
+        as_dot_tail(dr, s_w, &s_leave, t - 192, nd, tp.y + (int64_t)(par_ ^ 1) * cap * kAsD);
+        return;
       }
       as_lds_barrier();   // (2)
       as_lds_barrier();   // (3)
@@ -3651,6 +3734,12 @@ __global__ __launch_bounds__(kAsIterT) void k_as_iter(const int32_t* stopw, cons
             fma(b45.y, x[5], fma(b45.x, x[4], fma(b23.y, x[3], fma(b23.x, x[2], fma(b01.y, x[1], b01.x * x[0])))));
       }
     }
+    if (wave < 8 + kDotBW) {
+      AsDotRow dr;
+      as_dot_load(tp, c, t - 192, dr);
+      as_dot_tail(dr, s_w, &s_leave, t - 192, nd, tp.y + (int64_t)(par_ ^ 1) * cap * kAsD);
+      return;
+    }
     as_lds_barrier();   // (2)
     as_lds_barrier();   // (3)
     return;
@@ -3661,7 +3750,6 @@ __global__ __launch_bounds__(kAsIterT) void k_as_iter(const int32_t* stopw, cons
     const int k2 = ts < kGS ? ts : kGS - 1;
     const int4 cn = tp.con[(int64_t)c * kGS + k2];
     const int nd = rt[25], ns = rt[27];
-    const int ry = min(ts >> 1, kAsD - 1), hl = ts & 1;
     asm volatile("" ::: "memory");
     stop_ep = __builtin_amdgcn_readfirstlane(stop_ep);
     if (stop_ep != 0) return;
@@ -3713,37 +3801,9 @@ __global__ __launch_bounds__(kAsIterT) void k_as_iter(const int32_t* stopw, cons
         for (int j = 0; j < 6; ++j) s_m[6 * kk + j] = mv[j];
       }
     as_lds_barrier();   // (1)
-    // the inverse rows now (only the last phase reads them; issued with the first trip they queued the whole
-    // workgroup's small loads behind 46 KB per workgroup)
-    uint4 z[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) z[k] = tp.slab[((int64_t)c * kAsK + 9 * hl + k) * kAsD + ry];
-    const float dsc_r = tp.dsc[(int64_t)c * kAsD + ry];
-    as_lds_barrier();   // (2)
-    as_lds_barrier();   // (3)
-    if (s_leave) return;   // (converged: no contributions; the row waves took the leave path)
-    // y_c = D Ẑ (D w): k_as_apply's segment dot (two lanes, four chains, the pair summed by DPP) times the row scale
-    const double2* w2p = reinterpret_cast<const double2*>(s_w);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    auto lo = [](uint32_t u) { return (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(u & 0xFFFFu)); };
-    auto hi = [](uint32_t u) { return (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16)); };
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int kw = 9 * hl + k;
-      const double2 p0 = w2p[4 * kw], p1 = w2p[4 * kw + 1], p2 = w2p[4 * kw + 2], p3 = w2p[4 * kw + 3];
-      a0 = fma(lo(z[k].x), p0.x, a0);
-      a1 = fma(hi(z[k].x), p0.y, a1);
-      a2 = fma(lo(z[k].y), p1.x, a2);
-      a3 = fma(hi(z[k].y), p1.y, a3);
-      a0 = fma(lo(z[k].z), p2.x, a0);
-      a1 = fma(hi(z[k].z), p2.y, a1);
-      a2 = fma(lo(z[k].w), p3.x, a2);
-      a3 = fma(hi(z[k].w), p3.y, a3);
-    }
-    double dot = (a0 + a1) + (a2 + a3);
-    dot += dpp_mov<0xB1>(dot);   // quad_perm [1, 0, 3, 2]: the row's two halves
-    if (hl == 0 && ts < 2 * kAsD && (ts >> 1) < 6 * nd)
-      tp.y[(int64_t)(par_ ^ 1) * cap * kAsD + (int64_t)c * kAsD + (ts >> 1)] = (double)dsc_r * dot;
+    AsDotRow dr;
+    as_dot_load(tp, c, ts, dr);
+    as_dot_tail(dr, s_w, &s_leave, ts, nd, tp.y + (int64_t)(par_ ^ 1) * cap * kAsD);
     return;
   }
   // ---------------- rows: wave 0 the own rows (k_pcg_iter's wave), 1-2 the ring rows (ghost z, w)
@@ -3993,9 +4053,10 @@ __global__ __launch_bounds__(kAsIterT) void k_as_w0(GnDev g, const double* rhs, 
     int2 be[kP];
 #pragma unroll
     for (int j = 0; j < kP; ++j) be[j] = tp.blk[(int64_t)c * kGB + (tb + kGB * j) / 6];
-    const int nb = rt[26];
+    const int nb = rt[26], nd = rt[25];
     asm volatile("" ::: "memory");
     if (stopped) return;
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): trip 1 landed (k_as_iter's: the A rows' groups then issue together)
     const double2* A2 = reinterpret_cast<const double2*>(g.Aop);
     double2 ar[kP][3];
 #pragma unroll
@@ -4016,6 +4077,12 @@ __global__ __launch_bounds__(kAsIterT) void k_as_w0(GnDev g, const double* rhs, 
         s_prod[pp] = ((b01.x * x[0] + b01.y * x[1]) + (b23.x * x[2] + b23.y * x[3])) + (b45.x * x[4] + b45.y * x[5]);
       }
     }
+    if (wave < 8 + kDotBW) {
+      AsDotRow dr;
+      as_dot_load(tp, c, t - 192, dr);
+      as_dot_tail(dr, s_w, nullptr, t - 192, nd, tp.y);
+      return;
+    }
     as_lds_barrier();   // (2)
     as_lds_barrier();   // (3)
     return;
@@ -4029,7 +4096,6 @@ __global__ __launch_bounds__(kAsIterT) void k_as_w0(GnDev g, const double* rhs, 
     if (kGather) cn = tp.con[(int64_t)c * kGS + k2];
     else s2u = tp.s2n[(int64_t)c * kGS + k2];
     const int nd = rt[25], ns = rt[27];
-    const int ry = min(ts >> 1, kAsD - 1), hl = ts & 1;
     asm volatile("" ::: "memory");
     if (stopped) return;
     const double* yr = tp.y + (int64_t)g.as_tab_cap * kAsD;   // (y[1])
@@ -4077,34 +4143,9 @@ __global__ __launch_bounds__(kAsIterT) void k_as_w0(GnDev g, const double* rhs, 
         for (int k = 0; k < 6; ++k) s_m[6 * kk + k] = mv[k];
       }
     as_lds_barrier();   // (1)
-    uint4 z[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) z[k] = tp.slab[((int64_t)c * kAsK + 9 * hl + k) * kAsD + ry];
-    const float dsc_r = tp.dsc[(int64_t)c * kAsD + ry];
-    as_lds_barrier();   // (2)
-    as_lds_barrier();   // (3)
-    // y_c = D Ẑ (D w0): k_as_iter's (k_as_apply's) segment dot times the row scale
-    const double2* w2p = reinterpret_cast<const double2*>(s_w);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    auto lo = [](uint32_t u) { return (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(u & 0xFFFFu)); };
-    auto hi = [](uint32_t u) { return (double)(float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16)); };
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int kw = 9 * hl + k;
-      const double2 p0 = w2p[4 * kw], p1 = w2p[4 * kw + 1], p2 = w2p[4 * kw + 2], p3 = w2p[4 * kw + 3];
-      a0 = fma(lo(z[k].x), p0.x, a0);
-      a1 = fma(hi(z[k].x), p0.y, a1);
-      a2 = fma(lo(z[k].y), p1.x, a2);
-      a3 = fma(hi(z[k].y), p1.y, a3);
-      a0 = fma(lo(z[k].z), p2.x, a0);
-      a1 = fma(hi(z[k].z), p2.y, a1);
-      a2 = fma(lo(z[k].w), p3.x, a2);
-      a3 = fma(hi(z[k].w), p3.y, a3);
-    }
-    double dot = (a0 + a1) + (a2 + a3);
-    dot += dpp_mov<0xB1>(dot);   // the row's two halves
-    if (hl == 0 && ts < 2 * kAsD && (ts >> 1) < 6 * nd)
-      tp.y[(int64_t)c * kAsD + (ts >> 1)] = (double)dsc_r * dot;   // (parity 0: the first iteration's)
+    AsDotRow dr;
+    as_dot_load(tp, c, ts, dr);
+    as_dot_tail(dr, s_w, nullptr, ts, nd, tp.y);
     return;
   }
   // ---------------- rows: wave 0 the own rows (k_pcg_w0's wave), 1-2 the ring rows (w0 for the image only)
@@ -4216,10 +4257,10 @@ __global__ __launch_bounds__(512) void k_as_proj2(GnDev g, const double* rhs, in
       const double2 p0 = w2p[4 * kw], p1 = w2p[4 * kw + 1], p2 = w2p[4 * kw + 2], p3 = w2p[4 * kw + 3];
       a0 = fma(lo(z[k].x), p0.x, a0);
       a1 = fma(hi(z[k].x), p0.y, a1);
-      a2 = fma(lo(z[k].y), p1.x, a2);
-      a3 = fma(hi(z[k].y), p1.y, a3);
-      a0 = fma(lo(z[k].z), p2.x, a0);
-      a1 = fma(hi(z[k].z), p2.y, a1);
+      a2 = fma(lo(z[k].z), p1.x, a2);
+      a3 = fma(hi(z[k].z), p1.y, a3);
+      a0 = fma(lo(z[k].y), p2.x, a0);
+      a1 = fma(hi(z[k].y), p2.y, a1);
       a2 = fma(lo(z[k].w), p3.x, a2);
       a3 = fma(hi(z[k].w), p3.y, a3);
     }

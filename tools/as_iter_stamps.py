@@ -1,4 +1,5 @@
-"""Tuning study (not product): per-phase clock stamps of the one-launch Schwarz iteration (k_as_iter) on a 2k-node frame.
+"""Tuning study (not product): per-phase clock stamps of the one-launch Schwarz iteration (k_as_iter) on a 1.9k-node frame
+(argument: the node count).
 
 Needs the stamps build: python -c "from occlusionfusion_amd import build; build.build(out='tools/stampslib/libofx_stamps.so',
 defines=['OFX_STAMPS'])", then OFX_LIB=tools/stampslib/libofx_stamps.so python tools/as_iter_stamps.py
@@ -22,7 +23,7 @@ fn = _lib.lib.ofx_gn_stamps
 fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
 fn.restype = ctypes.c_int32
 dev = torch.device("cuda", 0)
-seq = S.SyntheticSequence.build(2000, seed=3)
+seq = S.SyntheticSequence.build(int(sys.argv[1]) if len(sys.argv) > 1 else 1900, seed=3)   # (<= 256 clusters: one launch)
 D = 128
 pipe = FusionPipeline(seq, (-D * 0.002, -D * 0.002, 0.5), 0.004, (D, D, D), device=dev)
 frames = [pipe.prepare(t) for t in range(8)]
@@ -77,7 +78,7 @@ for it in range(1, 60):
 if spans:
     print(f"  per-XCD span (first entry -> last end): median {np.median(spans):.0f}, p90 {np.percentile(spans, 90):.0f};"
           f" entry offsets p90 {np.median(ent):.0f}")
-    tc = np.array(tot_c)
-    print(f"  per-cluster totals: median {np.median(tc):.0f}, max over the XCD median {np.median(tc.max(axis=1)):.0f}")
+    print(f"  per-cluster totals: median {np.median(np.concatenate(tot_c)):.0f}, max over the XCD median "
+          f"{np.median([x.max() for x in tot_c]):.0f}")
     top = np.argsort(-late)[:8]
     print("  clusters most often last on their XCD:", [(int(c), int(late[c])) for c in top])
