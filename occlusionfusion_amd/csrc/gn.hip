@@ -1,424 +1,9 @@
-// Gauss-Newton non-rigid registration solver: block-sparse JᵀJ / Jᵀr assembly + block-Jacobi PCG.
-//
-// Restates DeformNet.optimize (model/model.py:222-859) for one batch item:
-//   unknowns per node i: [ω_i (3) | t_i (3)]  (reference orders all rotations, then all translations;
-//                                              the dense oracle maps between the two orders)
-//   data rows (3 per match, model.py:416-545): p = Σ_k w_k (R_k(x-g_k)+g_k+t_k)
-//       r  = [lf(fx·px/z+cx-tpx) + ld(px-tx), lf(fy·py/z+cy-tpy) + ld(py-ty), ld(pz-tz)]
-//       ∂/∂t_k = w_k·[[lf·fx/z+ld, 0, lf·(-fx·px/z²)], [0, lf·fy/z+ld, lf·(-fy·py/z²)], [0,0,ld]]
-//       ∂/∂ω_k = S + [[-fx·px/z²·S₂ ], [-fy·py/z²·S₂], [0]] + lf·[[fx/z·S₀],[fy/z·S₁],[0]],  S = -[w_k R_k(x-g_k)]×
-//       (the un-weighted -f·p/z² terms reproduce the operator-precedence quirk at model.py:505-510)
-//   ARAP rows (3 per directed edge, model.py:554-601): r = la·w(R_i(g_j-g_i)+g_i+t_i-g_j-t_j)
-//   motion rows (3 per node, model.py:604-612):       r = lm·c_i(t_i+g_i-target_i)
-//   A = JᵀJ + λ_LM·I, b = -Jᵀr, λ_LM halved at gn_i ≡ 2 mod 3 (model.py:418-419, 641-662)
-//   x = A⁻¹b (reference: dense LU, model.py:59-86,694-709 -> here: f64 block-Jacobi PCG)
-//   early stop on loss increase > stop_diff or unchanged loss (model.py:726-732), then
-//   R ← exp([x_ω]) R (kornia 0.7 angle_axis_to_rotation_matrix), t += x_t (model.py:744-748).
-//
-// MI355X design.
-//  * Every residual row-triple is a "term" (data: 4 anchored nodes, ARAP edge: 2, motion: 1). Once per GN
-//    iteration k_terms writes each term's compact record (kRec doubles: the per-anchor vectors and the
-//    term's shared scalars, not its four 3x6 Jacobian blocks); the assembly expands a record into the
-//    blocks it needs with the same arithmetic, so A and b are the bits the blocks themselves gave.
-//  * JᵀJ lives as 6x6 f64 blocks in BSR over the node adjacency (diagonal, edges, co-anchored
-//    pairs). Per solve, each block gets a sorted list of the (term, p, q) products that land on it,
-//    so assembly is a deterministic gather: one wave per block, lane = block entry (k_blocks); the
-//    rhs is the same per node entry (k_rhs). No atomics -> bitwise reproducible A and b.
-//  * Node order: setup groups the nodes into clusters of <= kCS graph neighbours (host BFS over the
-//    ED graph, first-fit packed into groups of exactly kCS rows, padded with decoupled dummy nodes),
-//    and permutes every node-indexed array into that order; k_finish permutes the result back.
-//  * PCG: pipelined (Ghysels-Vanroose) with a cluster block-Jacobi preconditioner (explicit inverse
-//    of each damped 48x48 cluster diagonal block), ONE kernel per iteration: SpMV + all recurrences
-//    + the cluster M⁻¹ (wave-local: one cluster = one wave's rows) + the three dot products. Scalars
-//    never leave the device: each launch writes per-wave partial sums and every wave of the NEXT
-//    launch re-derives the same scalars from them in a fixed order (kernel boundaries give
-//    visibility; no fences, no tickets, no atomics). The host only polls convergence in chunks
-//    sized from the previous frame's count for the same GN step.
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <chrono>
-#include <array>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <type_traits>
-#include <utility>
-#include <cstdlib>
-#include <cstdio>
-#include <vector>
-
-#include "ofx_common.h"
+// Gauss-Newton solver: the per-problem setup, the PCG and Schwarz kernels with the solve's launch loop, the GN step,
+// the prefetch worker and every ofx_gn_* entry point. Design and source map: gn_internal.h; the linearisation:
+// gn_linearize.hip.
+#include "gn_device.h"
 
 namespace ofx {
-
-// --------------------------------------------------------------------------------------------
-constexpr int kBlk = 256;       // threads per WG
-#ifndef OFX_KPROJ   // (tuning builds: -DOFX_KPROJ=<n>)
-#define OFX_KPROJ 4
-#endif
-constexpr int kProj = OFX_KPROJ;   // warm start: Galerkin projection on the last kProj GN-step solutions
-constexpr int kProjP = kProj * (kProj + 1) / 2 + kProj;   // projection partial streams (Gram upper triangle + Xᵀb)
-constexpr int kCS = 8;        // nodes per preconditioner cluster (= PCG rows per wave)
-constexpr int kMaxNodes = 8192;   // dense slot map of (2·max_nodes + kCS)² entries
-constexpr int kDirectMaxNodes = 512;   // OFX_PRECOND_DIRECT: 3072 unknowns, a 75 MB dense f64 buffer (ofx_spd_solve's limit)
-// Overlapping additive Schwarz (as_on): the ring of a cluster holds its kAsRing A-neighbours with the most coupling terms,
-// and a row joins at most kAsX rings, so an output cluster has at most kAsSrc contributing subdomains and kAsRS row
-// segments (a kAsD-entry inverse row each); kAsGat >= kAsSrc·kAsDN rounded up to whole passes of the apply's 192
-#ifndef OFX_AS_RING   // (tuning builds: -DOFX_AS_RING=<n>; 12 -> 16: 198 -> 158 PCG iterations per bench frame, +10 %)
-#define OFX_AS_RING 16
-#endif
-constexpr int kAsRing = OFX_AS_RING, kAsX = 3, kAsDN = kCS + kAsRing, kAsD = 6 * kAsDN, kAsK = kAsD / 8,
-              kAsSrc = 1 + kCS * kAsX, kAsRS = 6 * kCS * (1 + kAsX),
-              kAsGat = (kAsSrc * kAsDN + kAsRS - 1) / kAsRS * kAsRS, kAsMeta = 64 + kAsRS;
-// One launch per Schwarz PCG iteration (k_as_iter, round 6): per subdomain a table of its rows' blocks (<= kAsDN rows of
-// <= kRowMax blocks), the columns they touch (S2, <= kGS nodes) with the <= 1 + kAsX subdomain contributions that sum to m
-// there, and the scaled inverse rows in subdomain order (the "tab" buffer, AsTab below)
-constexpr int kGB = 512, kGS = 480, kGRow = 96;
-constexpr int kAsIterT = 1024;   // k_as_iter's threads: blocks 0..511, S2 nodes from 512, the row waves 13..15
-static_assert(kAsSrc * kAsDN <= kAsGat && kAsD % 8 == 0 && kAsD <= 144, "Schwarz tables");
-
-// Everything the kernels read: trivially copyable, passed by value as the kernel argument (host-only
-// members live in Gn below, so a launch copies these bytes and nothing else).
-struct GnDev {
-  int max_nodes = 0, max_matches = 0;
-  int N = 0, M = 0, NB = 0;    // N: PCG rows (nodes in cluster order, padded to whole clusters)
-  int N_real = 0;              // caller's node count
-  int max_pad = 0;             // capacity of the node-indexed arrays (2·max_nodes + kCS)
-  int32_t *perm = nullptr;     // row -> caller node (-1: padding), N entries
-  int32_t *iperm = nullptr;    // caller node -> row, N_real entries
-  int64_t T = 0;        // terms = M + N*NB + N
-  ofx_gn_params prm{};
-  float fx = 0, fy = 0, cx = 0, cy = 0;
-  // problem (f64 device copies)
-  double *nodes = nullptr, *tpos = nullptr, *conf = nullptr, *src = nullptr, *wts = nullptr, *tgt = nullptr,
-         *tpx = nullptr, *tpy = nullptr, *ew = nullptr;
-  int32_t *anc = nullptr, *edges = nullptr;
-  // terms
-  int32_t* term_node = nullptr;  // T*4, -1 = unused entry
-  double* J = nullptr;           // T·kRec term records (k_terms)
-  double* res = nullptr;         // T*3
-  int64_t T_cap = 0;
-  // pattern + contribution lists
-  int32_t *map = nullptr, *row_ptr = nullptr, *col = nullptr, *row_cnt = nullptr;   // row_cnt[N]: max row length
-  int2* wl = nullptr;            // per PCG wave: its first kWL blocks' columns and packed row bounds (k_wave_list)
-  double* Aw = nullptr;          // per PCG wave: its kWL blocks of the operator, [wave][18][kWL] 16-B words (k_pcg_w0)
-  int max_deg = 0;               // longest block row of the pattern
-  int max_wave = 0;              // most blocks of one PCG wave (kCS rows)
-  int32_t* stopw = nullptr;      // per PCG wave and lane: the epoch of the last converged (or stopped) PCG solve
-  int32_t ep = 0;                // epoch of the current PCG solve (one per GN step, increasing per handle)
-  uint64_t* stamps = nullptr;    // tuning builds (-DOFX_STAMPS): per iteration < 64 and wave, 8 clock stamps
-  int32_t* blk_row = nullptr;    // block -> row (clears the slot map's pattern at the next setup)
-  float* d_gnodes = nullptr;      // device copy of the graph the row order was built for (optimistic check)
-  int32_t* d_gedges = nullptr;
-  int32_t* d_gdiff = nullptr;
-  int64_t gcap_n = 0, gcap_e = 0;
-  int pat_N = 0;                 // N and block count of the pattern currently set in `map`
-  int64_t pat_nnzb = 0;
-  int64_t ne_cap = 0;            // capacity of edges / ew
-  // contribution lists of the UPPER blocks only (col >= row, indexed u = up_of[slot]): the assembly computes each
-  // upper block once and also stores its transpose at up_tr[u], so A is exactly symmetric. (A separate gather of the
-  // lower block (j, i) would sum the same products in the same order only when no node repeats within a term; with
-  // a repeated anchor its last bits could differ from the transpose.)
-  int32_t *blk_off = nullptr, *blk_cnt = nullptr, *blk_list = nullptr, *blk_tmp = nullptr;
-  int32_t *up_of = nullptr, *up_slot = nullptr, *up_tr = nullptr;   // slot -> u (+ total at [nnzb]), u -> slot, transpose
-  int32_t *node_off = nullptr, *node_cnt = nullptr, *node_list = nullptr, *node_tmp = nullptr;
-  // the first chunk of every assembly workgroup's list (kCoop codes) and of every node's rhs list (128), at fixed
-  // offsets (k_first_codes): k_assemble's first memory trip carries them
-  int32_t *blk_first = nullptr, *node_first = nullptr;
-  int64_t nnzb = 0, nnzb_cap = 0;
-  // state
-  double *R = nullptr, *t = nullptr;
-  double* racc = nullptr;        // per row: Σ|ω| of the GN steps since its cluster inverse was built (precond_rot_tol)
-  int32_t gn_iter_now = 0;       // GN step of the current PCG solve
-  double *A_own = nullptr, *rhs_own = nullptr;
-  float* Mcl = nullptr;           // cluster inverses, f32, per cluster 48x48 in the lane-interleaved order of mcl_idx
-  const double* Aop = nullptr;    // PCG operator (the damped A of the current step)
-  double *st = nullptr;          // PCG recurrence state, 6N records of 8 (see the PCG layout note)
-  double *m0 = nullptr, *m1 = nullptr;   // double-buffered m = M⁻¹w (gathered by the SpMV)
-  double *pcg_alpha = nullptr, *pcg_gamma = nullptr;   // [-, -, 1/x of parity 0, 1] (+ alpha: [4 + par] = thr)
-  // pcg_alpha, pcg_gamma, scal, sturm and flags live in ONE allocation at fixed offsets (kSc*), so the PCG iteration
-  // reaches all of them through one preloaded pointer argument (no kernel-argument fetch ahead of their loads)
-  double* pcs = nullptr;
-  double2* sturm = nullptr;       // error-based PCG stop (k_pcg_iter): 64 shifted LDLᵀ pivots + counts
-  double *part_p = nullptr, *part_b = nullptr, *part_loss = nullptr;
-  int32_t nwg_row = 0, nwg_node = 0, nwg_terms = 0;   // nwg_row: PCG row waves (= workgroups)
-  int32_t nw_pad = 0;            // stride of the iteration partial streams: 128·pcg_ku, zero beyond nwg_row
-  int32_t pcg_w2 = 1;            // two waves per cluster in k_pcg_iter (OFX_PCG_W1=1: one)
-  int32_t pcg_ku = 3;            // partial pairs per lane and stream in k_pcg_iter (pcg_ku_for)
-  // overlapping additive Schwarz preconditioner (as_on): subdomain D_c = cluster c's kCS rows + up to kAsRing
-  // ring rows; the setup's tables (k_as_choose .. k_as_segments) and the prep's inverses (k_as_invert), applied by
-  // k_as_apply between two PCG iteration launches
-  int32_t as_on = 0;
-  int32_t *as_cand = nullptr, *as_csc = nullptr, *as_acc = nullptr;   // [cluster][kAsRing]: ring candidates, terms, kept
-  int32_t* as_dom = nullptr;     // [cluster][kAsDN]: the subdomain's rows (own rows first, -1 = none)
-  int32_t* as_meta = nullptr;    // [cluster][kAsMeta]: segment count, source count, row offsets, segment -> source slot
-  int32_t* as_gat = nullptr;     // [cluster][kAsGat]: rows gathered into the apply's LDS image (source slot · kAsDN + l)
-  int32_t* as_dst = nullptr;     // [cluster][kAsD]: subdomain row -> (output cluster · kAsRS + segment)
-  uint16_t* as_slab = nullptr;   // [cluster][kAsK][kAsRS] x 8 fp16: the segments' scaled inverse rows, segment-minor
-  int32_t* as_src = nullptr;     // [cluster][kAsSrc]: the apply's source subdomains
-  float* as_dsc = nullptr;       // [cluster][kAsD]: the subdomain inverse's scales d = √diag(Z) (k_as_invert)
-  float* as_rsc = nullptr;       // [cluster][kAsRS]: the segment rows' scales
-  double* as_w = nullptr;        // 6N: the vector the next apply reads (w of the iteration, r0, ...)
-  // one launch per iteration (k_as_iter, as_one): the per-subdomain tables, ghost (w, z) of the ring rows, the parity's
-  // contributions y_c = Z_c w[D_c] and the subdomain-ordered inverse rows, in ONE buffer (offsets: AsTab)
-  int32_t as_one = 0, as_tab_cap = 0;
-  char* as_tab = nullptr;
-  int32_t *as_mem = nullptr, *as_memn = nullptr;   // per row: its subdomain memberships (c·kAsD + 6·l, <= 1 + kAsX)
-  double* scal = nullptr;
-  int32_t* flags = nullptr;
-  // DeformNet.arap mode with lambda_flow = 0: rows of each multi-node connected graph component
-  // (comp_off[c]..comp_off[c+1] in comp_rows), whose common translation is the exact null space
-  int32_t *comp_rows = nullptr, *comp_off = nullptr;
-  int n_comp = 0, comp_cap = 0;
-  double* loss_log = nullptr;
-  double* stat = nullptr;         // kMaxLog x [pcg iterations, |b|², loss] of the last solve
-  double* step_state = nullptr;   // (kMaxLog+1) x [previous loss, accepted steps] before each GN step
-  // Galerkin warm start over the last kProj GN-step solutions of this solve (ring of kProj x 6N each;
-  // the previous frame's solutions were measured not to help its first steps):
-  // xh = previous solutions, th = A·xh
-  double *xh = nullptr, *th = nullptr;
-  struct StepArgs* step_args = nullptr;   // device copy (fused GN step in the converging PCG launch)
-  bool step_fused = false;                // this step's k_step work was done by the PCG
-  int n_prev = 0;                 // valid entries of the ring for the current step
-  int warm_now = 0;               // this step starts from the projected x0
-  int32_t* host_flags = nullptr;  // pinned, mapped: [H_DONE, H_PCG_IT, H_STOPPED] written by the kernels
-  int32_t* hflags = nullptr;      // its device address (system-scope stores: no copy kernel per poll)
-  int32_t* setup_stat = nullptr;  // pinned, mapped: the setup's one host read [nnz, max row, max wave, abort, graph diff]
-  int32_t* d_setup_stat = nullptr;
-  hipEvent_t poll_ev = nullptr;   // recorded after each chunk of PCG launches
-  double host_enqueue_us = 0.0;   // tuning build: host time spent enqueuing PCG iterations
-  int64_t host_enqueued = 0;
-  bool setup_done = false;
-  // optional timing of the PCG iteration loop (hipEvents on the caller's stream)
-  bool timing = false;
-  int64_t n_iter_launches = 0;
-};
-static_assert(std::is_trivially_copyable<GnDev>::value, "kernel argument");
-
-// The as_tab buffer (k_as_iter), for a capacity of cap clusters: region by region, [cluster][...] each (16-B aligned)
-//   blk  [kGB]  int2  the subdomain rows' blocks in row order (CSR order within a row): (A slot, S2 index << 5 | row)
-//   con  [kGS]  int4  per S2 node the y indices (c'·kAsD + 6·l') of the subdomains holding it, ascending, -1 after
-//   s2n  [kGS]  int   S2 node -> row (the first iteration gathers m from the warm start's m0)
-//   row  [kGRow] int  row starts [0, kAsDN], then nd at 25, nb at 26, ns at 27; S2 index of each subdomain row at 32 + l,
-//                     its node (row) at 64 + l
-//   dsc  [kAsD] f32   the inverse's scales d = √diag Z (k_as_invert)
-//   gh   [kAsRing·6] double2  ghost (w, z) of the ring rows (the owners' recurrences, repeated bit for bit)
-//   y    [2][cap][kAsD] f64  per parity the contributions y_c = D Ẑ D w[D_c]
-//   slab [kAsK][kAsD] uint4  Ẑ's rows (8 fp16 per word, its 32-bit pairs in the order 0, 2, 1, 3: a lane pair of the
-//                     contribution dot takes 8-B halves), word k of every row contiguous
-struct AsTabP {
-  int2* blk; int4* con; int32_t* s2n; int32_t* row; float* dsc; double2* gh; double* y; uint4* slab;
-};
-__host__ __device__ __forceinline__ AsTabP as_tab_at(char* base, int64_t cap) {
-  AsTabP p;
-  char* q = base;
-  p.blk = reinterpret_cast<int2*>(q); q += cap * kGB * 8;
-  p.con = reinterpret_cast<int4*>(q); q += cap * kGS * 16;
-  p.s2n = reinterpret_cast<int32_t*>(q); q += cap * kGS * 4;
-  p.row = reinterpret_cast<int32_t*>(q); q += cap * kGRow * 4;
-  p.dsc = reinterpret_cast<float*>(q); q += cap * kAsD * 4;
-  p.gh = reinterpret_cast<double2*>(q); q += cap * kAsRing * 6 * 16;
-  p.y = reinterpret_cast<double*>(q); q += 2 * cap * kAsD * 8;
-  p.slab = reinterpret_cast<uint4*>(q);
-  return p;
-}
-static inline int64_t as_tab_bytes(int64_t cap) {
-  return cap * ((int64_t)kGB * 8 + (int64_t)kGS * 16 + (int64_t)kGS * 4 + kGRow * 4 + kAsD * 4 + kAsRing * 6 * 16 +
-                2 * kAsD * 8 + (int64_t)kAsK * kAsD * 16);
-}
-
-// The solver handle: the kernel-visible state plus host-only members.
-struct Gn : GnDev {
-  std::vector<float> h_nodes;          // host copy of the graph the current order was built from
-  std::vector<int32_t> h_edges, h_perm;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // timing events of the PCG loops
-  // converged PCG iteration count of the previous solve, per GN step (sizes the first chunk of launches);
-  // shared by the solver slots of one frame loop (ofx_gn_share_history)
-  struct PcgHist {                  // per GN step the converged counts of the last 4 solves (ring), newest at n % 4
-    int c[64][4] = {};
-    int n[64] = {};
-  };
-  std::shared_ptr<PcgHist> last_pcg = std::make_shared<PcgHist>();
-  // prefetched setup (ofx_gn_prepare): the next problem's setup runs on a host thread, on the handle's own
-  // stream, while the caller's stream still works on the current problem (of another handle)
-  std::thread worker;               // persistent (created by the first prefetch): no per-frame thread start
-  std::mutex mu;
-  std::condition_variable cv;
-  bool job = false, quit = false;   // guarded by mu: a prefetch is queued / running; shut down
-  // guarded by mu: a queued prefetch waits for its trigger (ofx_gn_prepare_after) — another handle's solve
-  // reaching a GN step, that solve returning, or a wait on this handle
-  bool gate = false;
-  Gn* pf_peer = nullptr;            // (trigger side) the handle whose gated prefetch this handle's next solve opens
-  int pf_step = 0;                  // ... at the start of this GN step (or on return)
-  Gn* pf_trigger = nullptr;         // (prefetch side) the handle holding this one as pf_peer
-  int prep_dev = 0;
-  int prep_status = 0;
-  bool prepared = false;            // the setup of prep_pb / prep_prm is (being) enqueued on `side`
-  ofx_gn_problem prep_pb{};
-  ofx_gn_params prep_prm{};
-  hipStream_t side = nullptr;
-  hipEvent_t ev_in = nullptr, ev_prep = nullptr;   // caller's stream at prepare -> side; side's setup done
-  // side-stream work of a prefetch that no caller stream has been ordered after yet: the worker returns before
-  // its last kernels (row assignment, contribution lists, ...) have run, and they write this handle's buffers
-  bool side_dirty = false;
-  hipEvent_t ev_side = nullptr;
-  int64_t pf_used = 0, pf_missed = 0;   // solves that used / discarded a prefetched setup
-  int32_t ep_next = 1;
-  int as_env = -1;                  // OFX_PRECOND override of params.precond (-1: none; 3: direct)
-  // exact dense solve (OFX_PRECOND_DIRECT, OFX_GN_OPTIMIZE): the dense lower triangle (dn_n x dn_n, row-major) and b / x
-  // of the 6·N_real unknowns in caller node order, allocated at the first setup that asks for it and kept
-  int direct = 0;                   // the last setup's solver: 1 = dense Cholesky instead of the PCG
-  int dn_n = 0, dn_cap = 0;
-  double *dn_A = nullptr, *dn_b = nullptr;
-  int32_t* dn_status = nullptr;     // ofx_spd_solve's status of the current GN step
-  void (*idle_fn)(void*) = nullptr; // ofx_gn_set_idle_hook: host work run once at the next solve's first PCG wait
-  void* idle_arg = nullptr;
-  int as_lanes = 2;                 // k_as_apply's lanes per segment (OFX_AS_LANES)
-  int as_cap = 0;                   // clusters the Schwarz tables are allocated for
-  // the PCG iteration's constant launch arguments (struct PcgIt) in device memory, and the bytes last copied there
-  void* d_pcgit = nullptr;
-  alignas(16) unsigned char pcgit_last[512] = {};
-  bool pcgit_valid = false;
-#ifdef OFX_STAMPS   // tuning build: stream idle between a PCG chunk's last launch and the next GN step's first kernel
-  std::chrono::steady_clock::time_point t_seen{};   // host saw the step's convergence
-  double react_us = 0.0, prologue_us = 0.0;         // -> k_terms enqueued; -> the first PCG chunk launch enqueued
-  int64_t react_n = 0;
-  hipEvent_t gap_end = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> gap_ev;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> entry_ev;   // solve entry -> pose done (the prefetched setup's wait)
-  double prep_wait_us = 0.0;
-#endif
-};
-
-// Order stream hs after everything the prefetch worker enqueued on the handle's side stream (call after
-// prep_wait: the worker has finished enqueuing). Every entry point that touches the handle's buffers on a
-// caller stream does this first, whether or not the prefetched setup is used.
-static int fence_side(Gn* g, hipStream_t hs) {
-  if (!g->side || !g->side_dirty) return OFX_OK;
-  OFX_HIP(hipEventRecord(g->ev_side, g->side));
-  OFX_HIP(hipStreamWaitEvent(hs, g->ev_side, 0));
-  g->side_dirty = false;
-  return OFX_OK;
-}
-// the same for host reads of device buffers (synchronous copies do not order after a non-blocking stream)
-static int sync_side(Gn* g) {
-  if (!g->side || !g->side_dirty) return OFX_OK;
-  OFX_HIP(hipStreamSynchronize(g->side));
-  g->side_dirty = false;
-  return OFX_OK;
-}
-
-// F_REFRESH: the GN step whose warm start rebuilds the cluster inverse (set by the previous step's update when a node's
-// accumulated rotation passed precond_rot_tol; 0 = none); F_CAPPED: GN steps whose PCG ran into pcg_max_iter
-enum { F_DONE = 0, F_STOPPED = 1, F_ILL = 2, F_ACCEPTED = 3, F_PCG_TOTAL = 4, F_APPLY = 5, F_RES_NONFINITE = 6,
-       F_PCG_IT = 7, F_PCG_CNT = 8, F_REFRESH = 9, F_CAPPED = 10, F_COUNT = 11 };
-// scalars: S_TH_CUR = the current solve's latest θ̂ (error-based stop), S_TH_PREV = the previous GN step's final θ̂
-// (k_pcg_w0 moves it per solve; 1e300 = none)
-enum { S_LOSS_PREV = 0, S_BB = 1, S_TH_PREV = 2, S_TH_CUR = 3, S_COUNT = 4 };
-// host-mapped flags: H_DONE holds the epoch (GnDev::ep) of the last converged PCG solve (from the converging launch's
-// lead lane);
-// H_STOPPED the epoch of the solve whose GN step stopped the loop (0: running). k_upload clears them per setup.
-enum { H_DONE = 0, H_PCG_IT = 1, H_STOPPED = 2, H_COUNT = 3 };
-__device__ __forceinline__ void host_flag(const int32_t* hf, int k, int v) {
-  __hip_atomic_store(const_cast<int32_t*>(hf) + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-constexpr int kMaxLog = 64;   // per-GN-step statistics slots
-constexpr int32_t kEpochWrap = 1 << 30;   // GnDev::ep restarts at 1 from a setup once it reaches this (a solve adds <= 64)
-
-// the scalar block (GnDev::pcs), in doubles: pcg_alpha [0, 6), pcg_gamma [6, 12), scal [12, 16), sturm (64 double2)
-// [16, 144), flags (int32) from 144; written by k_pcg_w0 per solve: the PCG operator's address at 150, the stop tolerances
-// (pcg_tol, pcg_err_tol) at 152, 153, the cluster inverses' address at 154, m0 / m1's at 156 / 157. The iteration gets
-// the block's address with its parity in bit 3 (the block is 256-B aligned), so it needs no kernel-argument fetch for
-// any of them.
-constexpr int kPcgStreams = 4;   // k_pcg_iter's per-wave partial streams per parity: γ = r·u, δ = w·u, r·r, p·p
-constexpr int kScAlpha = 0, kScGamma = 6, kScScal = 12, kScSturm = 16, kScFlags = 144, kScAop = 150, kScTol = 152,
-              kScMcl = 154, kScM = 156, kScSize = 160;
-
-// ---------------------------------------------------------------------------- reductions
-template <int CTL>
-__device__ __forceinline__ double dpp_mov(double x) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// Sum over each aligned 16-lane row; every lane of the row ends with identical bits.
-__device__ __forceinline__ double row16_sum(double x) {
-  x += dpp_mov<0xB1>(x);    // quad_perm [1,0,3,2]
-  x += dpp_mov<0x4E>(x);    // quad_perm [2,3,0,1]
-  x += dpp_mov<0x141>(x);   // row_half_mirror
-  x += dpp_mov<0x140>(x);   // row_mirror
-  return x;
-}
-__device__ __forceinline__ double read_lane(double x, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
-// x from the lanes selected by a broadcast DPP control into the rows of row_mask (0 elsewhere)
-template <int CTL, int ROWS>
-__device__ __forceinline__ double dpp_bcast(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTL, ROWS, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTL, ROWS, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// Full-wave sum, fixed order, uniform result. Call from wave-uniform control flow. After the 16-lane row sums r0..r3,
-// row_bcast:15 adds row 0 into row 1 and row 2 into row 3, row_bcast:31 adds row 1 into row 3, whose lane 63 then
-// holds (r3 + r2) + (r1 + r0) — bitwise the (r0 + r1) + (r2 + r3) of reading four lanes (f64 addition commutes
-// exactly), in 2 DPP adds and one lane read instead of 4 lane reads, 2 moves back to VGPRs and 3 adds.
-__device__ __forceinline__ double wave_sum(double x) {
-  x = row16_sum(x);
-  x += dpp_bcast<0x142, 0xA>(x);   // row_bcast:15 into rows 1, 3
-  x += dpp_bcast<0x143, 0x8>(x);   // row_bcast:31 into row 3
-  return read_lane(x, 63);
-}
-// four block sums at once: fixed-order wave sums, then the kBlk/64 wave results combined in wave order
-__device__ __forceinline__ void block_sum4(double v[4]) {
-  __shared__ double s4[kBlk / 64][4];
-  const int w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = wave_sum(v[k]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s4[w][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    double a = 0.0;
-#pragma unroll
-    for (int q = 0; q < kBlk / 64; ++q) a += s4[q][k];
-    v[k] = a;
-  }
-}
-__device__ __forceinline__ double block_sum(double v) {
-  __shared__ double s[kBlk];
-  s[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-    if (threadIdx.x < (unsigned)o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  double r = s[0];
-  __syncthreads();
-  return r;
-}
-
-// Sum of p[i*stride + off], i < n, in a fixed order; every thread of the WG gets the same bits.
-__device__ __forceinline__ double wg_sum_fixed(const double* __restrict__ p, int n, int stride, int off) {
-  __shared__ double s_res;
-  if (threadIdx.x < 64) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) acc += p[(int64_t)i * stride + off];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (threadIdx.x == 0) s_res = acc;
-  }
-  __syncthreads();
-  double r = s_res;
-  __syncthreads();
-  return r;
-}
 
 // ---------------------------------------------------------------------------- setup kernels
 // graph unchanged since the row order was built? (bitwise compare; any difference sets *diff)
@@ -805,392 +390,6 @@ __global__ __launch_bounds__(256) void k_seg_rank(const int32_t* __restrict__ of
   }
 }
 
-// ---------------------------------------------------------------------------- linearisation
-struct DataCoef {
-  double lf, ld, la, lm, fx, fy, cx, cy;
-};
-
-// Compact term records (kRec doubles per term at J + t·kRec; 160 B against the 576 B of four 3x6 blocks):
-//   data  : [v_k w_k] for anchors k = 0..3 (v_k = w_k R_k(x - g_k)) at 4k, then [fx/z fy/z mfx mfy] at 16
-//   ARAP  : [d0 d1 d2 s] at 0 (node i: d = R_i(g_j - g_i), s = la·w_e), node j's diagonal -s at 4
-//   motion: the three diagonal entries at 0
-// term_block() expands (record, slot) into the 3x6 block with the arithmetic the blocks were written with,
-// operation for operation, so the assembled A and b are the same bits.
-constexpr int kRec = 20;
-
-// slot k of data term m: its anchor's [v w]; slot 0 also the term's shared scalars
-__device__ __forceinline__ void data_record(const GnDev& g, const DataCoef& dc, int64_t m, int k, const double p[3],
-                                            double zinv, double* __restrict__ rec) {
-  int a = g.anc[m * 4 + k];
-  double w = g.wts[m * 4 + k];
-  const double* R = g.R + 9 * (int64_t)a;
-  const double* gn = g.nodes + 3 * (int64_t)a;
-  double d0 = g.src[3 * m] - gn[0], d1 = g.src[3 * m + 1] - gn[1], d2 = g.src[3 * m + 2] - gn[2];
-  double2* o = reinterpret_cast<double2*>(rec + 4 * k);
-  o[0] = make_double2(w * (R[0] * d0 + R[1] * d1 + R[2] * d2), w * (R[3] * d0 + R[4] * d1 + R[5] * d2));
-  o[1] = make_double2(w * (R[6] * d0 + R[7] * d1 + R[8] * d2), w);
-  if (k == 0) {
-    double2* tl = reinterpret_cast<double2*>(rec + 16);
-    tl[0] = make_double2(dc.fx * zinv, dc.fy * zinv);
-    tl[1] = make_double2(-(dc.fx * p[0] * zinv) * zinv, -(dc.fy * p[1] * zinv) * zinv);
-  }
-}
-
-enum TermKind { kData = 0, kEdge = 1, kMotion = 2 };
-__device__ __forceinline__ int term_kind(const GnDev& g, int64_t t) {
-  return t < g.M ? kData : (t < g.M + (int64_t)g.N * g.NB ? kEdge : kMotion);
-}
-
-// the 3x6 block of `slot` from the record's words x = rec[4·slot .. +3] and (data) tail = rec[16 .. 19]
-__device__ __forceinline__ void term_block(int kind, int slot, const double x[4], const double tail[4],
-                                           const DataCoef& dc, double J[18]) {
-#pragma unroll
-  for (int c = 0; c < 18; ++c) J[c] = 0.0;
-  if (kind == kData) {
-    const double v0 = x[0], v1 = x[1], v2 = x[2], w = x[3];
-    const double fxdz = tail[0], fydz = tail[1], mfx = tail[2], mfy = tail[3];
-    // S = -[v]x
-    const double S[9] = {0.0, v2, -v1, -v2, 0.0, v0, v1, -v0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      J[0 + j] = dc.lf * fxdz * S[0 + j] + mfx * S[6 + j] + dc.ld * S[0 + j];
-      J[6 + j] = dc.lf * fydz * S[3 + j] + mfy * S[6 + j] + dc.ld * S[3 + j];
-      J[12 + j] = dc.ld * S[6 + j];
-    }
-    J[3] = dc.lf * w * fxdz + dc.ld * w; J[5] = dc.lf * w * mfx;
-    J[10] = dc.lf * w * fydz + dc.ld * w; J[11] = dc.lf * w * mfy;
-    J[17] = dc.ld * w;
-  } else if (kind == kEdge && slot == 0) {   // node i: [-s[d]x | s I]
-    const double d0 = x[0], d1 = x[1], d2 = x[2], s = x[3];
-    J[1] = s * d2; J[2] = -s * d1; J[3] = s;
-    J[6] = -s * d2; J[8] = s * d0; J[10] = s;
-    J[12] = s * d1; J[13] = -s * d0; J[17] = s;
-  } else if (kind == kEdge) {                 // node j: [0 | -s I]
-    J[3] = x[0]; J[10] = x[0]; J[17] = x[0];
-  } else {
-    J[3] = x[0]; J[10] = x[1]; J[17] = x[2];
-  }
-}
-
-// the record words of (t, slot): two 16-B loads, plus the two of a data term's tail — loaded for every kind (every
-// record has them) and zeroed for the others: a load in a kind branch was waited for inside it, one term after another
-__device__ __forceinline__ void load_record(const GnDev& g, int64_t t, int slot, int kind, double x[4], double tail[4]) {
-  const double2* r = reinterpret_cast<const double2*>(g.J + t * kRec);
-  const double2 a = r[2 * slot], b = r[2 * slot + 1];
-  const double2 c = r[8], d = r[9];
-  x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
-  const bool dt = kind == kData;
-  tail[0] = dt ? c.x : 0.0; tail[1] = dt ? c.y : 0.0; tail[2] = dt ? d.x : 0.0; tail[3] = dt ? d.y : 0.0;
-}
-
-// Anchor k's summand of the deformed point of match m: w_k (R_k (x - g_k) + g_k + t_k) (ED_warp, geometry.py:9-25)
-__device__ __forceinline__ void anchor_term(const GnDev& g, int64_t m, int k, double c[3]) {
-  int a = g.anc[m * 4 + k];
-  double w = g.wts[m * 4 + k];
-  const double* R = g.R + 9 * (int64_t)a;
-  const double* gn = g.nodes + 3 * (int64_t)a;
-  const double* tt = g.t + 3 * (int64_t)a;
-  double d0 = g.src[3 * m] - gn[0], d1 = g.src[3 * m + 1] - gn[1], d2 = g.src[3 * m + 2] - gn[2];
-  c[0] = w * ((R[0] * d0 + R[1] * d1 + R[2] * d2) + gn[0] + tt[0]);
-  c[1] = w * ((R[3] * d0 + R[4] * d1 + R[5] * d2) + gn[1] + tt[1]);
-  c[2] = w * ((R[6] * d0 + R[7] * d1 + R[8] * d2) + gn[2] + tt[2]);
-}
-
-// Four threads per term (t = id/4, slot k = id%4): slot k writes its node's words of the term record
-// (kRec above); slot 0 also writes the residual triple and the loss partials. Terms outside this rank's
-// share (data matches outside [m0,m1), regularisers when !add_reg) get all-zero records (exact zero
-// blocks) so the fixed contribution lists stay valid.
-__global__ __launch_bounds__(kBlk) void k_terms(GnDev g, DataCoef dc, int m0, int m1, int add_reg) {
-  // every kernel-argument field in SGPRs up front, in one scalar trip (left to the compiler, each branch loaded its own
-  // fields after the branch: four dependent scalar trips ahead of the first vector load)
-  asm volatile("" :: "s"(g.J), "s"(g.anc), "s"(g.wts), "s"(g.R), "s"(g.nodes), "s"(g.src), "s"(g.t), "s"(g.tgt),
-               "s"(g.tpx), "s"(g.tpy), "s"(g.edges), "s"(g.ew), "s"(g.res), "s"(g.T), "s"(g.M), "s"(g.N), "s"(g.NB),
-               "s"(g.conf), "s"(g.tpos), "s"(g.prm.mode), "s"(g.part_loss), "s"(m0), "s"(m1), "s"(add_reg));
-  asm volatile("" :: "s"(dc.lf), "s"(dc.ld), "s"(dc.la), "s"(dc.lm), "s"(dc.fx), "s"(dc.fy), "s"(dc.cx), "s"(dc.cy));
-  const int64_t id = blockIdx.x * (int64_t)kBlk + threadIdx.x;
-  const int64_t t = id >> 2;
-  const int k = (int)(id & 3);
-  double r[3] = {0.0, 0.0, 0.0};
-  double l2[3] = {0.0, 0.0, 0.0};
-  double bad = 0.0;
-  if (t < g.T) {
-    double* rec = g.J + t * kRec;
-    if (t < g.M) {
-      if (t >= m0 && t < m1) {
-        // deformed point: slot k computes its anchor's summand, the four slots (adjacent lanes of one wave, all
-        // in this branch together) exchange them and every slot adds them to 0 in the anchor order k = 0..3
-        // (the oracle's sequence; each slot used to recompute all four summands itself: 13.2 -> 11.8 us)
-        // the residual's target values are loaded by every slot up front (no trip behind the k == 0 branch)
-        const double tpx = g.tpx[t], tpy = g.tpy[t];
-        const double tg0 = g.tgt[3 * t], tg1 = g.tgt[3 * t + 1], tg2 = g.tgt[3 * t + 2];
-        double c[3];
-        anchor_term(g, t, k, c);
-        const int base = (int)(threadIdx.x & 63) & ~3;
-        double p[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-          for (int d = 0; d < 3; ++d) p[d] += __shfl(c[d], base + kk, 64);
-        double zinv = 1.0 / (p[2] + 1e-7);
-        data_record(g, dc, t, k, p, zinv, rec);
-        if (k == 0) {
-          r[0] = dc.lf * (dc.fx * p[0] * zinv + dc.cx - tpx) + dc.ld * (p[0] - tg0);
-          r[1] = dc.lf * (dc.fy * p[1] * zinv + dc.cy - tpy) + dc.ld * (p[1] - tg1);
-          r[2] = dc.ld * (p[2] - tg2);
-          l2[0] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-        }
-      } else {
-        double2* o = reinterpret_cast<double2*>(rec + 4 * k);
-        o[0] = o[1] = make_double2(0.0, 0.0);
-        if (k == 0) reinterpret_cast<double2*>(rec + 16)[0] = reinterpret_cast<double2*>(rec + 16)[1] = make_double2(0.0, 0.0);
-      }
-    } else if (t < g.M + (int64_t)g.N * g.NB) {
-      const int64_t e = t - g.M;
-      const int j = g.edges[e];
-      // the edge's weight and node i's R, g, t leave with the edge's j (none depends on j; behind the j >= 0 test the
-      // weight was a trip of its own, then i's and j's records another)
-      const int i = (int)(e / g.NB);
-      const double ewv = g.ew[e];
-      double Ri[9], gi[3], ti[3];
-#pragma unroll
-      for (int q = 0; q < 9; ++q) Ri[q] = g.R[9 * (int64_t)i + q];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) { gi[q] = g.nodes[3 * (int64_t)i + q]; ti[q] = g.t[3 * (int64_t)i + q]; }
-      asm volatile("" ::: "memory");
-      if (j >= 0 && k < 2) {
-        if (add_reg) {
-          const double s = dc.la * ewv;
-          if (k == 0) {
-            const double* gj = g.nodes + 3 * (int64_t)j;
-            const double* tj = g.t + 3 * (int64_t)j;
-            double e0 = gj[0] - gi[0], e1 = gj[1] - gi[1], e2 = gj[2] - gi[2];
-            double d0 = Ri[0] * e0 + Ri[1] * e1 + Ri[2] * e2;
-            double d1 = Ri[3] * e0 + Ri[4] * e1 + Ri[5] * e2;
-            double d2 = Ri[6] * e0 + Ri[7] * e1 + Ri[8] * e2;
-            r[0] = s * (d0 + gi[0] + ti[0] - (gj[0] + tj[0]));
-            r[1] = s * (d1 + gi[1] + ti[1] - (gj[1] + tj[1]));
-            r[2] = s * (d2 + gi[2] + ti[2] - (gj[2] + tj[2]));
-            double2* o = reinterpret_cast<double2*>(rec);   // node i's [d s]
-            o[0] = make_double2(d0, d1);
-            o[1] = make_double2(d2, s);
-            l2[1] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-          } else {  // node j's diagonal
-            rec[4] = -s;
-          }
-        } else if (k == 0) {
-          reinterpret_cast<double2*>(rec)[0] = reinterpret_cast<double2*>(rec)[1] = make_double2(0.0, 0.0);
-          rec[4] = 0.0;
-        }
-      }
-    } else if (k == 0) {
-      const int i = (int)(t - g.M - (int64_t)g.N * g.NB);
-      double J3 = 0.0, J10 = 0.0, J17 = 0.0;
-      if (add_reg && g.prm.mode == OFX_GN_ARAP) {
-        // DeformNet.arap "flow" rows of the valid nodes (model.py:1766-1784): the Jacobian entry on
-        // t_c is the residual itself, as the reference writes it
-        const double c = dc.lf * g.conf[i];
-        for (int q = 0; q < 3; ++q) r[q] = c * (g.t[3 * i + q] + g.nodes[3 * i + q] - g.tpos[3 * i + q]);
-        J3 = r[0]; J10 = r[1]; J17 = r[2];
-        l2[0] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      } else if (add_reg) {
-        double c = dc.lm * g.conf[i];
-        for (int q = 0; q < 3; ++q) r[q] = c * (g.t[3 * i + q] + g.nodes[3 * i + q] - g.tpos[3 * i + q]);
-        J3 = c; J10 = c; J17 = c;
-        l2[2] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      }
-      rec[0] = J3; rec[1] = J10; rec[2] = J17;
-    }
-    if (k == 0) {
-      g.res[3 * t] = r[0]; g.res[3 * t + 1] = r[1]; g.res[3 * t + 2] = r[2];
-      bad = (isfinite(l2[0]) && isfinite(l2[1]) && isfinite(l2[2])) ? 0.0 : 1.0;
-    }
-  }
-  double sv[4] = {l2[0], l2[1], l2[2], bad};
-  block_sum4(sv);
-  if (threadIdx.x == 0) {
-    double* P = g.part_loss + 4 * (int64_t)blockIdx.x;
-    P[0] = sv[0]; P[1] = sv[1]; P[2] = sv[2]; P[3] = sv[3];
-  }
-}
-
-// b = -Jᵀr: one wave per node, entry-parallel (below). WG 0 also reduces the loss partials into the
-// rhs tail.
-__device__ __forceinline__ void rhs_body(const GnDev& g, const DataCoef& dc, double* __restrict__ rhs, int wg) {
-  if (wg == 0 && threadIdx.x < 64) {   // the loss partials of k_terms, 4 streams in one pass, fixed order
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < g.nwg_terms; i += 64) {
-      const double4 t = *reinterpret_cast<const double4*>(g.part_loss + 4 * (int64_t)i);
-      a[0] += t.x; a[1] += t.y; a[2] += t.z; a[3] += t.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
-    if (threadIdx.x == 0) {
-      double* tail = rhs + 6 * (int64_t)g.N;
-      tail[0] = a[0]; tail[1] = a[1]; tail[2] = a[2]; tail[3] = a[3];
-    }
-  }
-  const int n = wg * (kBlk / 64) + (threadIdx.x >> 6);
-  if (n >= g.N) return;
-  const int lane = threadIdx.x & 63;
-  // one wave per node, one list entry per lane (two per lane per pass: a busy node's ~90 terms in one
-  // pass of two dependent trips — code, then J + r — where 10 slots took ~10 serial passes); every load
-  // unconditional (clamped index, masked value) so no branch splits a trip; fixed-order wave sums
-  const int b = g.node_off[n], e = g.node_off[n + 1];
-  int code[2];   // the first pass's codes come with the bounds (node_first), later passes' from the list
-#pragma unroll
-  for (int j = 0; j < 2; ++j) code[j] = g.node_first[(int64_t)n * 128 + lane + 64 * j];
-  asm volatile("" ::: "memory");   // (issued with the bounds, not sunk into the loop behind its entry test)
-  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int k0 = b; k0 < e; k0 += 128) {
-    bool ok[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int k = k0 + lane + 64 * j;
-      ok[j] = k < e;
-      if (k0 != b) code[j] = g.node_list[ok[j] ? k : e - 1];
-    }
-    // both entries' records and residuals first (one trip), then the blocks (left in the loop, the second entry's loads
-    // issued after the first entry's kind branches: two trips)
-    int kind[2];
-    double x[2][4], tail[2][4], rv[2][3];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t t = code[j] >> 2;
-      kind[j] = term_kind(g, t);
-      load_record(g, t, code[j] & 3, kind[j], x[j], tail[j]);
-      const double* rr = g.res + 3 * t;
-      rv[j][0] = rr[0]; rv[j][1] = rr[1]; rv[j][2] = rr[2];
-    }
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      double P[18];
-      term_block(kind[j], code[j] & 3, x[j], tail[j], dc, P);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        const double t3 = P[c] * rv[j][0] + P[6 + c] * rv[j][1] + P[12 + c] * rv[j][2];
-        v[c] += ok[j] ? t3 : 0.0;
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) v[c] = wave_sum(v[c]);
-  if (lane == 0)
-#pragma unroll
-    for (int c = 0; c < 6; ++c) rhs[6 * (int64_t)n + c] = -v[c];
-}
-
-// JᵀJ blocks, workgroup-cooperative: the workgroup's 16 blocks own one contiguous range of the sorted
-// contribution list. Chunks of kCoop entries: one thread per entry loads its two Jacobian blocks (the next
-// chunk's codes one chunk ahead) and writes the full 6×6 product to LDS ([output][entry], padded: conflict-
-// free writes); then each (block, output) pair — 576 per workgroup, up to 3 per thread — adds its entries of
-// the chunk in list order. A block's cost is its share of the workgroup's entries, not its own list length
-// (the 16-lane form took ceil(len/16) dependent trips: ~6 for a busy node's diagonal block).
-#ifndef OFX_KCOOP
-#define OFX_KCOOP 128   // (tuning builds: -DOFX_KCOOP=n, n <= kBlk)
-#endif
-constexpr int kCoop = OFX_KCOOP;
-static_assert(kCoop <= kBlk, "one entry per thread per chunk");
-__device__ __forceinline__ void blocks_coop(const GnDev& g, const DataCoef& dc, double* __restrict__ A, int64_t wg,
-                                            double lm) {
-  __shared__ double s_prod[36 * (kCoop + 1)];
-  __shared__ int s_off[17];
-  const int tid = threadIdx.x;
-  const int64_t sb = wg * (kBlk / 16);   // upper blocks u in [sb, sb + 16); past the upper count up_slot is -1 and
-                                         // the lists are empty (blk_off there = the total)
-  constexpr int kPairs = (kBlk / 16) * 36;
-  constexpr int kU = (kPairs + kBlk - 1) / kBlk;
-  // first trip: the 17 list offsets and every pair's output slots (consumed at the end, in flight all along)
-  // (every load unconditional, the list offsets first: a load inside the offsets' branch was waited for there, before
-  // the other loads issued)
-  const int offv = g.blk_off[min<int64_t>(sb + min(tid, kBlk / 16), g.nnzb)];
-  int code_next = g.blk_first[wg * kCoop + min(tid, kCoop - 1)];   // the first chunk's codes (k_first_codes)
-  int pb[kU], po[kU], os[kU], ot[kU];
-#pragma unroll
-  for (int u = 0; u < kU; ++u) {
-    const int p = tid + kBlk * u;
-    pb[u] = p < kPairs ? p / 36 : kBlk / 16 - 1; po[u] = p % 36;
-    os[u] = g.up_slot[sb + pb[u]];
-    ot[u] = g.up_tr[sb + pb[u]];
-  }
-  if (tid <= kBlk / 16) s_off[tid] = offv;
-  __syncthreads();
-  const int E0 = s_off[0], E1 = s_off[kBlk / 16];
-  if (E0 == E1) return;   // no upper block here (uniform over the workgroup)
-  double acc[kU];
-  int lo[kU], hi[kU];
-#pragma unroll
-  for (int u = 0; u < kU; ++u) {
-    const bool ok = tid + kBlk * u < kPairs;
-    lo[u] = ok ? s_off[pb[u]] : 0;
-    hi[u] = ok ? s_off[pb[u] + 1] : 0;
-    acc[u] = 0.0;
-  }
-  for (int c0 = E0; c0 < E1; c0 += kCoop) {
-    if (tid < kCoop) {
-      const int k = c0 + tid;
-      const int code = code_next;
-      code_next = k + kCoop < E1 ? g.blk_list[k + kCoop] : 0;
-      if (k < E1) {
-        const int64_t t = code >> 4;
-        const int kind = term_kind(g, t), sp = (code >> 2) & 3, sq = code & 3;
-        double xp[4], xq[4], tail[4], P[18], Q[18];
-        load_record(g, t, sp, kind, xp, tail);
-        const double2* r = reinterpret_cast<const double2*>(g.J + t * kRec + 4 * sq);
-        const double2 a = r[0], b = r[1];
-        xq[0] = a.x; xq[1] = a.y; xq[2] = b.x; xq[3] = b.y;
-        term_block(kind, sp, xp, tail, dc, P);
-        term_block(kind, sq, xq, tail, dc, Q);
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-#pragma unroll
-          for (int j = 0; j < 6; ++j)
-            s_prod[(6 * c + j) * (kCoop + 1) + tid] = P[c] * Q[j] + P[6 + c] * Q[6 + j] + P[12 + c] * Q[12 + j];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int a = max(lo[u], c0), b = min(hi[u], c0 + kCoop);
-      const double* sp = s_prod + po[u] * (kCoop + 1) - c0;
-      double x = acc[u];
-      // eight LDS reads in flight, then the eight adds in list order (a one-read-per-add loop waited out the LDS
-      // latency per entry: a busy diagonal block's outputs cost ~90 serial round trips per chunk)
-      int e = a;
-      for (; e + 8 <= b; e += 8) {
-        double v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = sp[e + k];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x += v[k];
-      }
-      if (e + 4 <= b) {
-        double v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = sp[e + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x += v[k];
-        e += 4;
-      }
-      for (; e < b; ++e) x += sp[e];
-      acc[u] = x;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int u = 0; u < kU; ++u) {
-    const int p = tid + kBlk * u;
-    if (p >= kPairs || os[u] < 0) continue;
-    const int64_t s = os[u], st = ot[u];
-    double v = acc[u];
-    // LM damping of the diagonal blocks (model.py:641-662)
-    if (lm != 0.0 && po[u] % 7 == 0 && s == st) v += lm;
-    A[36 * s + po[u]] = v;
-    if (st != s) A[36 * st + 6 * (po[u] % 6) + po[u] / 6] = v;   // the lower block: the transpose
-  }
-}
-
 // The first chunk of every assembly workgroup's contribution list and of every node's rhs list at fixed offsets (setup,
 // after the lists are sorted): k_assemble loads them with the list bounds instead of one memory trip after them.
 __global__ __launch_bounds__(kBlk) void k_first_codes(GnDev g, int nwb) {
@@ -1205,35 +404,6 @@ __global__ __launch_bounds__(kBlk) void k_first_codes(GnDev g, int nwb) {
     g.node_first[(int64_t)n * 128 + t] = e > s0 ? g.node_list[s0 + t < e ? s0 + t : e - 1] : 0;
   }
 }
-
-// JᵀJ blocks and -Jᵀr in one launch: the rhs workgroups first (their per-node loops are the longest
-// chains), then nwb workgroups of blocks.
-__global__ __launch_bounds__(kBlk) __attribute__((amdgpu_waves_per_eu(4))) void k_assemble(GnDev g, DataCoef dc, double* __restrict__ A, double* __restrict__ rhs,
-                                                  int nrw, double lm) {
-  // the kernel-argument fields in SGPRs up front (one scalar trip, see k_terms; nrw, the rhs workgroup count, is an
-  // argument rather than gridDim.x - nwb: the grid size is one more scalar load)
-  asm volatile("" :: "s"(g.N), "s"(g.M), "s"(g.NB), "s"(g.node_list), "s"(g.node_off), "s"(g.nwg_terms),
-               "s"(g.part_loss), "s"(g.res), "s"(g.J), "s"(g.blk_list), "s"(g.blk_off), "s"(g.nnzb), "s"(g.up_slot),
-               "s"(g.up_tr), "s"(A), "s"(rhs), "s"(nrw), "s"(lm));
-  asm volatile("" :: "s"(dc.lf), "s"(dc.ld), "s"(dc.la), "s"(dc.lm), "s"(dc.fx), "s"(dc.fy), "s"(dc.cx), "s"(dc.cy));
-  // XCD-aware order: workgroups b and b + 8 share an XCD, so each XCD takes a contiguous run of nodes / upper
-  // blocks and the term records they share stay in one L2 (nrw is a multiple of 8, so both halves keep b % 8); a
-  // relabelling of which workgroup computes what: A and b are unchanged. Fetch 20.2 -> 7.9 MB per launch, time
-  // unchanged (the re-reads were served by the MALL): profiles/r05_ab.json
-  const int hw = blockIdx.x, part = hw < nrw ? nrw : (int)gridDim.x - nrw, i = hw < nrw ? hw : hw - nrw;
-  const int q = part >> 3, r = part & 7, x = i & 7;
-  const int L = x * q + min(x, r) + (i >> 3);
-  if (hw < nrw) rhs_body(g, dc, rhs, L);
-  else blocks_coop(g, dc, A, L, lm);
-}
-#ifdef OFX_SPLIT_ASSEMBLE
-__global__ __launch_bounds__(kBlk) void k_assemble_blocks(GnDev g, DataCoef dc, double* __restrict__ A, double lm) {
-  blocks_coop(g, dc, A, blockIdx.x, lm);
-}
-__global__ __launch_bounds__(kBlk) void k_assemble_rhs(GnDev g, DataCoef dc, double* __restrict__ rhs) {
-  rhs_body(g, dc, rhs, blockIdx.x);
-}
-#endif
 
 // ---------------------------------------------------------------------------- PCG
 // Pipelined preconditioned CG (Ghysels & Vanroose 2014): one global reduction per iteration, ONE
@@ -2986,48 +2156,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 // stop word: a converged (or broken-down) launch copies its wave's partials (rr = 0 on breakdown)
 // into the next parity and sets the stop words, so later launches of the chunk end after trip 1.
 // kWave = false: plain CSR rows (waves of more than kWL blocks or rows longer than kRowMax).
-// The iteration kernel's arguments: only what it reads (a ~200-B kernarg instead of the whole Gn:
-// the host enqueues ~1000 of these per frame, so per-launch host work is on the critical path).
-// What the converging PCG launch needs to also take the GN step (k_step's work, fused): fixed pointers in
-// device memory (written once at create), per-step values in the kernel arguments.
-struct StepArgs {
-  double *R, *t, *xh, *stat, *loss_log, *step_state;
-  const double* conf;
-  double* racc;
-};
-struct PcgIt {
-  const double* Aop;
-  const float* Mcl;
-  const int32_t *row_ptr, *col;
-  const int2* wl;
-  double *m0, *m1, *st, *part_p, *part_b, *pcg_alpha, *pcg_gamma, *scal;
-  int32_t *flags, *hflags, *stopw;
-  double2* sturm;               // error-based stop: per lead lane s the LDLᵀ pivot of T_k - σ_s I and its negative count
-  uint64_t* stamps;
-  int32_t nwg_row, nw_pad;
-  struct { double pcg_tol, pcg_err_tol; } prm;
-  // fused GN step (fuse = 0: k_step runs as its own launch)
-  const StepArgs* sa;
-  const double* tail;           // rhs + 6N: [loss² total, data, arap, motion, nonfinite]
-  double stop_loss_diff;
-  double rot_tol;               // precond_rot_tol
-  int32_t fuse, gn_iter, N, mode, n_iter_log, warm;
-  int32_t ep;                   // this solve's epoch (stop words, H_DONE)
-};
-static PcgIt pcg_args(const Gn* g) {
-  PcgIt a;
-  memset(&a, 0, sizeof(a));   // (padding too: the host compares copies bytewise)
-  a.Aop = g->Aop; a.Mcl = g->Mcl; a.row_ptr = g->row_ptr; a.col = g->col; a.wl = g->wl;
-  a.m0 = g->m0; a.m1 = g->m1; a.st = g->st; a.part_p = g->part_p; a.part_b = g->part_b;
-  a.pcg_alpha = g->pcg_alpha; a.pcg_gamma = g->pcg_gamma; a.scal = g->scal;
-  a.flags = g->flags; a.hflags = g->hflags; a.stopw = g->stopw; a.stamps = g->stamps;
-  a.nwg_row = g->nwg_row; a.nw_pad = g->nw_pad; a.prm.pcg_tol = g->prm.pcg_tol; a.prm.pcg_err_tol = g->prm.pcg_err_tol;
-  a.sturm = g->sturm;
-  a.sa = g->step_args; a.tail = nullptr; a.stop_loss_diff = g->prm.stop_loss_diff; a.rot_tol = g->prm.precond_rot_tol;
-  a.fuse = 0; a.gn_iter = 0; a.N = g->N; a.mode = g->prm.mode; a.n_iter_log = 64; a.warm = g->prm.pcg_warm;
-  a.ep = g->ep;
-  return a;
-}
 #ifdef OFX_STAMPS   // tuning build only: phase clock stamps of every wave of the first 64 iterations
 #define OFX_STAMP_AT(k)                                                                               \
   if (lane == 0 && g.stamps && cnt < 64) g.stamps[((int64_t)cnt * nw + wv) * 8 + (k)] = __builtin_amdgcn_s_memtime();
@@ -4487,13 +3615,6 @@ __global__ void k_finish(GnDev g, float* __restrict__ rot, float* __restrict__ t
 
 
 // --------------------------------------------------------------------------------------------
-static double lm_for_iter(double lm0, int gn_iter) {
-  double lm = lm0;
-  for (int i = 0; i <= gn_iter; ++i)
-    if (i % 3 == 2) lm /= 2;
-  return lm;
-}
-
 static void free_all(Gn* g) {
   void* ptrs[] = {g->nodes, g->tpos, g->conf, g->src, g->wts, g->tgt, g->tpx, g->tpy, g->ew, g->anc, g->edges,
                   g->term_node, g->J, g->res, g->map, g->row_ptr, g->col, g->blk_row, g->row_cnt, g->wl, g->Aw, g->stopw, g->blk_off, g->blk_cnt,
@@ -5666,32 +4787,7 @@ int ofx_gn_linearize(void* handle, int32_t gn_iter, int32_t m0, int32_t m1, int3
     g->gap_end = nullptr;
   }
 #endif
-  DataCoef dc;
-  dc.lf = sqrt(g->prm.lambda_flow); dc.ld = sqrt(g->prm.lambda_depth);
-  dc.la = sqrt(g->prm.lambda_arap); dc.lm = sqrt(g->prm.lambda_motion);
-  dc.fx = g->fx; dc.fy = g->fy; dc.cx = g->cx; dc.cy = g->cy;
-  hipLaunchKernelGGL(k_terms, dim3(g->nwg_terms), dim3(kBlk), 0, hs, *g, dc, m0, m1, add_reg);
-#ifdef OFX_STAMPS
-  if (gn_iter > 0 && g->t_seen.time_since_epoch().count()) {
-    g->react_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - g->t_seen).count();
-    ++g->react_n;
-  }
-#endif
-  // the LM damping λ_k I (model.py:418-419,641-662) is added by the rank that adds the regularisers, so a
-  // sum over ranks carries it once
-  const double lm = add_reg ? lm_for_iter(g->prm.lm_factor, gn_iter) : 0.0;
-  // upper blocks: (nnzb + diagonal blocks) / 2 <= (nnzb + rows) / 2 (the pattern is symmetric); workgroups past
-  // the device-side count return at once
-  const int nwb = g->nnzb > 0 ? (int)grid_for((g->nnzb + g->N) / 2 + 1, kBlk / 16, 1 << 30) : 0;
-#ifdef OFX_SPLIT_ASSEMBLE   // tuning build: the two halves as separate kernels (rocprof times each)
-  if (nwb) hipLaunchKernelGGL(k_assemble_blocks, dim3(nwb), dim3(kBlk), 0, hs, *g, dc, A, lm);
-  hipLaunchKernelGGL(k_assemble_rhs, dim3(grid_for(g->N, kBlk / 64)), dim3(kBlk), 0, hs, *g, dc, rhs);
-#else
-  const int nrw = ((int)grid_for(g->N, kBlk / 64) + 7) & ~7;   // (a multiple of 8: see k_assemble)
-  hipLaunchKernelGGL(k_assemble, dim3(nwb + nrw), dim3(kBlk), 0, hs, *g, dc, A, rhs, nrw, lm);
-#endif
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  return gn_linearize(g, gn_iter, m0, m1, add_reg, A, rhs, hs);
 }
 
 int ofx_gn_step(void* handle, int32_t gn_iter, double* A, double* rhs, ofx_stream_t s) {

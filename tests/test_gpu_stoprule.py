@@ -86,5 +86,10 @@ def test_stop_rule_is_one_constant_for_both_preconditioners():
     (no per-preconditioner factor): the defaults say 2e-6 = a fifth of the bar."""
     from occlusionfusion_amd.registration import GN_DEFAULTS
     assert GN_DEFAULTS["pcg_err_tol"] == 2e-6 and GN_DEFAULTS["pcg_tol"] == 2e-6
-    src = open(os.path.join(os.path.dirname(GOLDEN), "..", "occlusionfusion_amd", "csrc", "gn.hip")).read()
+    import glob
+    csrc = os.path.join(os.path.dirname(GOLDEN), "..", "occlusionfusion_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "gn*.hip")) + glob.glob(os.path.join(csrc, "gn*.h")))
+    assert files
+    src = "".join(open(f).read() for f in files)   # (the solver's sources: the store lives in one shared helper)
     assert "g.pcs[kScTol + 1] = g.prm.pcg_err_tol;" in src
+    assert src.count("kScTol + 1] =") == 1
