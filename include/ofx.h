@@ -36,6 +36,10 @@
  *   ofx_depth_mesh_*        compute_mesh_from_depth (pixel-grid mesh)       csrc/cpu/image_proc.cpp:405-545
  *                           (EDGraph.create_mesh_from_depth, WarpField.skin of an image: embedded_deformation_graph.py:95-151,
  *                           warpfield.py:160-175)
+ *   ofx_assoc_* / ofx_associate  (new) projective data association of model points with a depth frame — (no reference
+ *                           twin: the reference's matches come from learned front-ends; its geometric fallback is the
+ *                           truncated chamfer term, NonRigidICP/model/loss.py:275-292. Parity unpinned, as for ofx_raycast;
+ *                           restated op for op by tests/assoc_ref.py)
  *   ofx_depth_to_pc         Registration.optimize target cloud: depth_2_pc, NonRigidICP/model/geometry.py:44-59,
  *                           mask compaction, map_pixel_to_pcd              registration_fusion.py:104-109,388-395
  *   ofx_pixel_anchors_euclidean  csrc compute_pixel_anchors_euclidean     csrc/cpu/graph_proc.cpp:610-709
@@ -289,6 +293,58 @@ int ofx_depth_mesh_emit(void* handle, float* vertices, int32_t* vertex_pixels, i
  * Asynchronous (no host sync). */
 int ofx_depth_to_pc(void* handle, const float* depth, int32_t height, int32_t width, double fx, double fy, double cx,
                     double cy, float* points, int64_t* pix_map, int32_t* n_points, ofx_stream_t s);
+
+/* ---------------- Projective data association (new capability; the reference has none — parity unpinned) ----------------
+ * The data term of a depth frame without given matches: each model point is warped with the current node transforms, looked
+ * up in the target vertex map at its pixel, gated, and the surviving pairs are compacted for ofx_gn_solve (src / anchors /
+ * weights / tgt rows). Per point, the first rejection code that applies:
+ *   1  valid[p] == 0 (or an anchor outside [0, n_nodes): it cannot be gathered)
+ *   2  warped z <= 0, or non-finite, or the pixel outside the image
+ *   3  target depth at the pixel <= 0 (hole)
+ *   4  no target normal: the pixel on the image border, a 4-neighbour with z <= 0, a neighbour's z more than edge_max from
+ *      the centre's (depth edge), or a zero-length cross product
+ *   5  squared distance |q - x'|^2 > dist_max^2
+ *   6  normals given and n'.n_q < cos_min
+ *   0  accepted
+ * Arithmetic (f32, no contraction; every step fixed so that a numpy f32 restatement gives the same bits):
+ *   x'  = ofx_deform_points (normals = 0) of the point, bit for bit; n' = its normals = 1 form (the same device code);
+ *         a point with valid == 0 keeps its position in `warped`, as there
+ *   pixel = the one ofx_visibility_f32 takes for the f32 point x' (the same device function: (x.fx)/z + cx in f32 with a
+ *         correctly rounded division, rintf, the range test on the rounded value)
+ *   q   = point_image at the pixel (planar f32[3*H*W], the layout ofx_backproject_depth writes)
+ *   n_q = normalise((q[v,u+1] - q[v,u-1]) x (q[v+1,u] - q[v-1,u])): a*b - c*d per component, squared length (x^2 + y^2) +
+ *         z^2, square root and divisions correctly rounded; flipped if n_q.q > 0 (faces the camera). Dot products are
+ *         summed (x + y) + z
+ *   tgt = q (OFX_ASSOC_POINT) or x' + n_q*((q - x').n_q) (OFX_ASSOC_PLANE: the foot of x' on q's tangent plane; the solver's
+ *         3-D point rows then act as a point-to-plane term for the step and the surface can slide); zeros when rejected
+ * Compaction (scan of code == 0, ascending point index): with n accepted, all are emitted if n <= max_matches; otherwise
+ * the accepted point of rank r is emitted iff floor((r+1)*max_matches/n) > floor(r*max_matches/n) (64-bit integers) —
+ * exactly max_matches rows, evenly and deterministically, where the reference draws an unseeded randperm (model/model.py:
+ * 319-334). Emitted rows keep ascending point order: match_idx i32[max_matches] (point indices), src_out f32[.,3] (the
+ * un-warped points), tgt_out f32[.,3], anchors_out i32[.,4], weights_out f32[.,4]; count (DEVICE int32[2]) = [accepted,
+ * emitted]. Rows past `emitted` are left untouched.
+ * Per-point outputs: code u8[P], tgt f32[P,3], warped f32[P,3] (may be NULL). normals f32[P,3] and valid u8[P] may be NULL.
+ * anchors i32[P,4] / weights f32[P,4] (K = 4), their compacted twins and packed_nodes (ofx_pack_nodes) must be 16-byte
+ * aligned. cam's width / height must equal the image's. Stream-ordered: no allocation and no host sync inside the call;
+ * the handle owns the rank and tile scratch, sized at create for max_points (n_points above it is OFX_ERR_ARG).
+ * n_points = 0 is legal: count = [0, 0]. */
+typedef struct ofx_assoc_params {
+  float dist_max;        /* metres */
+  float cos_min;
+  float edge_max;        /* metres of z between 4-neighbours */
+  int32_t mode;          /* OFX_ASSOC_POINT / OFX_ASSOC_PLANE */
+  int32_t max_matches;   /* rows of the compacted outputs */
+  int32_t _pad;
+} ofx_assoc_params;
+enum { OFX_ASSOC_POINT = 0, OFX_ASSOC_PLANE = 1 };
+int ofx_assoc_create(int64_t max_points, void** handle);
+int ofx_assoc_destroy(void* handle);
+int ofx_associate(void* handle, const float* points, const float* normals, const int32_t* anchors, const float* weights,
+                  const uint8_t* valid, int64_t n_points, const float* packed_nodes, int32_t n_nodes,
+                  const ofx_camera* cam, const float* point_image, int32_t height, int32_t width,
+                  const ofx_assoc_params* prm, uint8_t* code, float* tgt, float* warped, int32_t* match_idx,
+                  float* src_out, float* tgt_out, int32_t* anchors_out, float* weights_out, int32_t* count,
+                  ofx_stream_t s);
 
 /* ---------------- Standalone skinning / anchors ---------------- */
 /* csrc twins, exact (Eigen summation order, list tie order, f32 weights): outputs (H, W, 4) images,

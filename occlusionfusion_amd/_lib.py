@@ -26,6 +26,11 @@ class Camera(ctypes.Structure):
                 ("height", c_int32)]
 
 
+class AssocParams(ctypes.Structure):
+    _fields_ = [("dist_max", c_float), ("cos_min", c_float), ("edge_max", c_float), ("mode", c_int32),
+                ("max_matches", c_int32), ("_pad", c_int32)]
+
+
 class GnParams(ctypes.Structure):
     _fields_ = [("num_iter", c_int32), ("use_edge_weighting", c_int32), ("pcg_max_iter", c_int32), ("pcg_warm", c_int32),
                 ("lambda_flow", c_double), ("lambda_depth", c_double), ("lambda_arap", c_double),
@@ -83,6 +88,9 @@ _SIGS = {
     "ofx_depth_mesh_count": [P, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_depth_mesh_emit": [P, P, P, P, P],
     "ofx_depth_to_pc": [P, P, c_int32, c_int32, c_double, c_double, c_double, c_double, P, P, P, P],
+    "ofx_assoc_create": [c_int64, P],
+    "ofx_assoc_destroy": [P],
+    "ofx_associate": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P],
     "ofx_pixel_anchors_euclidean": [P, c_int32, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_pixel_anchors_geodesic": [P, P, c_int32, c_int64, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_remap_anchors": [P, c_int64, P, c_int32, P, P],

@@ -1,0 +1,144 @@
+"""Projective data association: the matches of a depth frame, found by the library itself.
+
+Every solve here takes correspondences as an input; in the reference they come from learned front-ends (Lepard, the flow
+net). ProjectiveAssociator produces them from geometry alone, the way a TSDF fusion system tracks: warp the model points
+with the current estimate, look them up in the target depth frame's vertex map, gate by distance, depth edges and
+normals, and hand the surviving pairs to GaussNewtonSolver.optimize (torch.ops.ofx.associate -> ofx_associate, one gather
+kernel + an ordered compaction). It has no reference twin; its geometric relative there is the truncated chamfer term
+(NonRigidICP/model/loss.py:275-292). icp_track is the loop around it that Registration.track and
+FusionPipeline.track_step share. This is the data term for what the camera sees: motion of occluded nodes still needs the
+motion-completion input.
+"""
+import numpy as np
+import torch
+
+from . import _lib, ops  # noqa: F401  (ops registers torch.ops.ofx.*)
+from ._lib import byref, call
+
+MODES = {"point": 0, "plane": 1}
+CODE_NAMES = ("accepted", "invalid_skin", "off_image", "hole", "no_normal", "too_far", "normal_mismatch")
+ASSOC_DEFAULTS = dict(dist_max=0.05, cos_min=0.5, edge_max=0.03, mode="plane", max_matches=10000)
+
+
+class TooFewMatches(RuntimeError):
+    """An association emitted fewer matches than a solve needs (4·K = 16): nothing was solved."""
+
+
+def _f32(x, device, shape=None):
+    if x is None:
+        return None
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
+    t = t.to(device=device, dtype=torch.float32).contiguous()
+    return t if shape is None else t.reshape(shape)
+
+
+def pack_transforms(nodes, rot, trans, device):
+    """(N,16) packed node records (ofx_pack_nodes) of node positions (N,3), rotations (N,3,3) or None (identity) and
+    node-relative translations (N,3) or None (zero)."""
+    g = _f32(nodes, device, (-1, 3))
+    N = g.shape[0]
+    R = _f32(rot, device, (N, 9)) if rot is not None else torch.eye(3, device=device).reshape(1, 9).repeat(N, 1)
+    T = _f32(trans, device, (N, 3)) if trans is not None else torch.zeros((N, 3), device=device)
+    out = torch.empty((N, 16), dtype=torch.float32, device=device)
+    call("ofx_pack_nodes", _lib.ptr(R), _lib.ptr(T), _lib.ptr(g), N, _lib.ptr(out),
+         _lib.stream_ptr(torch.cuda.current_stream(device)))
+    return out
+
+
+class ProjectiveAssociator:
+    """Owns an ofx_assoc handle (rank and tile scratch for up to max_points points) and the last call's outputs."""
+
+    def __init__(self, max_points, device=None):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.max_points = int(max_points)
+        self._h = _lib.c_void_p()
+        with torch.cuda.device(self.device):
+            call("ofx_assoc_create", self.max_points, byref(self._h))
+        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)   # ofx::associate ordering token
+        self.last = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.lib.ofx_assoc_destroy(h)
+            except Exception:
+                pass
+        self._h = None
+
+    def associate(self, points, normals, anchors, weights, valid, warpfield_or_packed_nodes, point_image, intr,
+                  dist_max=0.05, cos_min=0.5, edge_max=0.03, mode="plane", max_matches=10000):
+        """Associate points (P,3) — skinned with anchors i32 (P,4) / weights (P,4), valid (P,) or None, unit normals
+        (P,3) or None — with the target vertex map point_image (3,H,W) (backproject_depth_device) under the transforms
+        of a WarpField or of a packed (N,16) node tensor (WarpField.packed_nodes / pack_transforms). intr: (fx, fy, cx,
+        cy). Gates: dist_max and edge_max in metres, cos_min on the warped normal against the target's; mode "plane"
+        targets the foot of the warped point on the target's tangent plane, "point" the vertex itself.
+
+        Returns a dict: the compacted matches sliced to the emitted count — match_idx (point indices, ascending),
+        src, tgt, anchors, weights — the per-point code (0 accepted, 1..6 the first gate that rejected the point;
+        CODE_NAMES), tgt_all, warped, and accepted / emitted / histogram (counts per code).
+
+        Reading the counts is the tracking loop's one host synchronisation per association; everything else is
+        enqueued on torch's current stream."""
+        d = self.device
+        pts = _f32(points, d, (-1, 3))
+        P = pts.shape[0]
+        if P > self.max_points:
+            raise ValueError(f"{P} points exceed the associator's capacity ({self.max_points})")
+        packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
+                  else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
+        a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
+        a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
+        v = None
+        if valid is not None:
+            v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
+            v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
+        vm = _f32(point_image, d)
+        assert vm.dim() == 3 and vm.shape[0] == 3, "point image must be (3, H, W)"
+        out = torch.ops.ofx.associate(self._state, self._h.value, pts, _f32(normals, d, (P, 3)), a,
+                                      _f32(weights, d, (P, 4)), v, packed, vm, [float(x) for x in intr[:4]],
+                                      float(dist_max), float(cos_min), float(edge_max), MODES[mode], int(max_matches))
+        code, tgt_all, warped, midx, src, tgt, a_o, w_o, count = out
+        hist = torch.bincount(code.to(torch.int64), minlength=len(CODE_NAMES))
+        host = torch.cat([count.to(torch.int64), hist]).cpu().tolist()   # the one host sync
+        n_acc, n_emit = int(host[0]), int(host[1])
+        self.last = {"match_idx": midx[:n_emit], "src": src[:n_emit], "tgt": tgt[:n_emit], "anchors": a_o[:n_emit],
+                     "weights": w_o[:n_emit], "code": code, "tgt_all": tgt_all, "warped": warped, "accepted": n_acc,
+                     "emitted": n_emit, "histogram": [int(x) for x in host[2:2 + len(CODE_NAMES)]]}
+        return self.last
+
+
+def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
+              valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3, **assoc):
+    """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
+    associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
+    matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
+    0, so the motion rows vanish. An association that emits fewer than 4·K = 16 matches raises TooFewMatches before any
+    solve. -> (the last optimize result, [per iteration dict(accepted, emitted, histogram)], vertex map)."""
+    from .image_proc import backproject_depth_device
+    if int(icp_iters) < 1:
+        raise ValueError("icp_iters must be at least 1")
+    d = solver.device
+    prm = dict(ASSOC_DEFAULTS)
+    unknown = set(assoc) - set(prm)
+    if unknown:
+        raise TypeError(f"unknown association parameters {sorted(unknown)}")
+    prm.update(assoc)
+    if int(prm["max_matches"]) > solver.max_matches:
+        prm["max_matches"] = solver.max_matches
+    fx, fy, cx, cy = (float(v) for v in intr[:4])
+    dep = depth if isinstance(depth, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(depth, np.float32))
+    vm = backproject_depth_device(dep.to(device=d, dtype=torch.float32), fx, fy, cx, cy)
+    tloc, tconf = complete_node_motion_data if complete_node_motion_data is not None else (None, None)
+    rot, trans, out, log = prev_rot, prev_trans, None, []
+    for it in range(int(icp_iters)):
+        m = associator.associate(points, normals, anchors, weights, valid, pack_transforms(graph_nodes, rot, trans, d),
+                                 vm, (fx, fy, cx, cy), **prm)
+        log.append({"accepted": m["accepted"], "emitted": m["emitted"], "histogram": m["histogram"]})
+        if m["emitted"] < 16:
+            raise TooFewMatches(f"projective association {it} emitted {m['emitted']} matches of {m['accepted']} accepted "
+                                f"({dict(zip(CODE_NAMES, m['histogram']))}); at least 16 (4·K) are needed to solve")
+        out = solver.optimize(graph_nodes, graph_edges, graph_edges_weights, tloc, tconf, m["src"], m["anchors"],
+                              m["weights"], m["tgt"], (fx, fy, cx, cy), prev_rot=rot, prev_trans=trans)
+        rot, trans = out["node_rotations"], out["node_translations"]
+    return out, log, vm

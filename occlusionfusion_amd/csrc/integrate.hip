@@ -25,44 +25,9 @@
 #include <vector>
 
 #include "ofx_common.h"
+#include "warp_device.h"
 
 namespace ofx {
-
-struct CamD {
-  double fx, fy, cx, cy;
-  float fxf, fyf, cxf, cyf;   // the same intrinsics as f32 (exact: ofx_camera is f32)
-  int W, H;
-};
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// Warp one voxel position with its K anchors (f32, reference op order). Rows 0 and 1 of R(x-g)+g+t
-// run as packed f32 pairs (v_pk_mul/add_f32; the same per-component rounding), row 2 scalar.
-// Node record layout: see ofx_pack_nodes.
-__device__ __forceinline__ void ed_warp(const float4* __restrict__ nodes, const int ids[4], const float w[4], int K,
-                                        float& x, float& y, float& z) {
-  f2 axy = {0.f, 0.f};
-  float az = 0.f;
-  const f2 xy = {x, y};
-  for (int k = 0; k < K; ++k) {
-    const float4* n = nodes + 4 * (int64_t)ids[k];
-    const float4 a = n[0], b = n[1], c = n[2], d = n[3];
-    const f2 P0 = {a.x, a.y}, P1 = {a.z, a.w}, P2 = {b.x, b.y}, G = {b.z, b.w}, T = {c.x, c.y};
-    const f2 dxy = xy - G;
-    const float dz = z - d.y;
-    f2 r = P0 * dxy.x;
-    r = r + P1 * dxy.y;
-    r = r + P2 * dz;
-    float rz = c.z * dxy.x;
-    rz = rz + c.w * dxy.y;
-    rz = rz + d.x * dz;
-    const f2 yxy = ((r + G) + T) * w[k];
-    const float yz = ((rz + d.y) + d.z) * w[k];
-    if (k == 0) { axy = yxy; az = yz; }
-    else { axy = axy + yxy; az = az + yz; }
-  }
-  x = axy.x; y = axy.y; z = az;
-}
 
 // Projection + visibility (tsdf.py:351-364, 576-612). Returns pixel index or -1.
 __device__ __forceinline__ int64_t project(const CamD& c, float x, float y, float z, double& Z) {
@@ -73,8 +38,6 @@ __device__ __forceinline__ int64_t project(const CamD& c, float x, float y, floa
   if (!(u >= 0.0 && u < (double)c.W && v >= 0.0 && v < (double)c.H && Z > 0.0)) return -1;
   return (int64_t)v * c.W + (int64_t)u;
 }
-
-__device__ __forceinline__ float cdiv(float a, float b) { return (float)((double)a / (double)b); }
 
 // s lies within tol of a rounding tie of rint (a half-integer)
 __device__ __forceinline__ bool near_half(double s, double tol) {
@@ -832,27 +795,10 @@ __global__ __launch_bounds__(256) void k_deform_points(const float* __restrict__
     int ids[4];
     float w[4];
     for (int k = 0; k < K; ++k) { ids[k] = anchors[p * K + k]; w[k] = weights[p * K + k]; }
-    if (!normals) {
-      ed_warp(nodes, ids, w, K, x, y, z);
-    } else {
-      // WarpField.deform_normals: deform_lbs with zero translation, weights==0 skipped (warpfield.py:208-231,312-345)
-      float ax = 0.f, ay = 0.f, az = 0.f;
-      for (int k = 0; k < K; ++k) {
-        if (w[k] == 0.f) continue;
-        const float4* nd = nodes + 4 * (int64_t)ids[k];
-        const float4 a = nd[0], b = nd[1], c = nd[2], d = nd[3];   // record layout: ofx_pack_nodes
-        float rx = a.x * x; rx = rx + a.z * y; rx = rx + b.x * z;
-        float ry = a.y * x; ry = ry + a.w * y; ry = ry + b.y * z;
-        float rz = c.z * x; rz = rz + c.w * y; rz = rz + d.x * z;
-        ax = ax + w[k] * rx; ay = ay + w[k] * ry; az = az + w[k] * rz;
-      }
-      x = ax; y = ay; z = az;
-    }
+    if (!normals) ed_warp(nodes, ids, w, K, x, y, z);
+    else ed_warp_normal(nodes, ids, w, K, x, y, z);
   }
-  if (normals) {
-    float nrm = (float)sqrt((double)((x * x + y * y) + z * z));
-    x = cdiv(x, nrm); y = cdiv(y, nrm); z = cdiv(z, nrm);
-  }
+  if (normals) normalise3(x, y, z);
   out[3 * p] = x; out[3 * p + 1] = y; out[3 * p + 2] = z;
 }
 
@@ -887,17 +833,8 @@ __global__ __launch_bounds__(256) void k_deform_lbs(const float* __restrict__ pt
   out[3 * p] = ox; out[3 * p + 1] = oy; out[3 * p + 2] = oz;
 }
 
-// F32: the projection of f32 points as numba types cam2pix on an f32 array (tsdf.py:351-364 called from
-// get_visible_nodes with the f32 deformed nodes, tsdf.py:614-638): (x·fx)/z + cx in f32 with the f32 intrinsics,
-// np.round (half-even) in f32, int(); the depth lookup and the difference stay f64 as get_depth_from_image's
-// np.zeros array makes them (tsdf.py:576-612). F32 = false: the f64 form of the integrate path (f64 cam_pts).
-__device__ __forceinline__ int64_t project_f32(const CamD& c, float x, float y, float z) {
-  const float su = cdiv(x * c.fxf, z) + c.cxf, sv = cdiv(y * c.fyf, z) + c.cyf;
-  const float u = rintf(su), v = rintf(sv);
-  if (!(u >= 0.0f && u < (float)c.W && v >= 0.0f && v < (float)c.H && z > 0.0f)) return -1;
-  return (int64_t)v * c.W + (int64_t)u;
-}
-
+// F32: the f32 projection of numba's cam2pix on an f32 array (project_f32, warp_device.h); F32 = false: the f64 form of
+// the integrate path (f64 cam_pts).
 template <bool F32>
 __global__ void k_visibility(const float* __restrict__ pts, int64_t n, CamD c, const float* __restrict__ depth,
                              double trunc, uint8_t* __restrict__ valid, double* __restrict__ ddiff) {
@@ -915,14 +852,6 @@ __global__ void k_visibility(const float* __restrict__ pts, int64_t n, CamD c, c
   double dd = dv - Z;
   valid[p] = (dv > 0.0 && dd >= -trunc) ? 1 : 0;
   if (ddiff) ddiff[p] = dd;
-}
-
-static CamD make_cam(const ofx_camera* cam) {
-  CamD c;
-  c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy;
-  c.fxf = cam->fx; c.fyf = cam->fy; c.cxf = cam->cx; c.cyf = cam->cy;
-  c.W = cam->width; c.H = cam->height;
-  return c;
 }
 
 }  // namespace ofx

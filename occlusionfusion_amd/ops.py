@@ -189,6 +189,51 @@ def _(points, anchors, weights, valid, packed_nodes, normals):
     return torch.empty_like(points)
 
 
+# --------------------------------------------------------------------------------------------- data association
+@_op("associate", mutates_args=("state",))
+def associate(state: Tensor, handle: int, points: Tensor, normals: Optional[Tensor], anchors: Tensor, weights: Tensor,
+              valid: Optional[Tensor], packed_nodes: Tensor, point_image: Tensor, intr: List[float], dist_max: float,
+              cos_min: float, edge_max: float, target_mode: int, max_matches: int
+              ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """ofx_associate (new capability, no reference twin): projective association of the points (P,3), skinned with
+    anchors / weights (P,4), warped by packed_nodes, with the vertex map point_image (3,H,W) -> per point code u8 (P,)
+    (0 = accepted, 1..6 the first gate that rejected it), tgt (P,3), warped (P,3); compacted, at their full max_matches
+    size (rows past count[1] are zero): match_idx i32, src (.,3), tgt (.,3), anchors i32 (.,4), weights (.,4); count
+    int32[2] on the device = [accepted, emitted]. target_mode: 0 point, 1 plane foot (not `mode`: that name is taken by
+    torch's functionalisation wrapper). `handle` is an ofx_assoc_create handle
+    sized for at least P points; `state` is its ordering token (its scratch is hidden state)."""
+    P, M = points.shape[0], int(max_matches)
+    dev = points.device
+    _, H, W = point_image.shape
+    cam = _camera(intr, H, W)
+    prm = _lib.AssocParams(float(dist_max), float(cos_min), float(edge_max), int(target_mode), M, 0)
+    v = None if valid is None else valid.to(torch.uint8)
+    code = torch.empty(P, dtype=torch.uint8, device=dev)
+    tgt = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    warped = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    midx = torch.zeros(M, dtype=torch.int32, device=dev)
+    src_o = torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    tgt_o = torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    a_o = torch.zeros((M, 4), dtype=torch.int32, device=dev)
+    w_o = torch.zeros((M, 4), dtype=torch.float32, device=dev)
+    count = torch.empty(2, dtype=torch.int32, device=dev)
+    call("ofx_associate", _lib.c_void_p(handle), ptr(points), ptr(normals), ptr(anchors), ptr(weights), ptr(v), P,
+         ptr(packed_nodes), packed_nodes.shape[0], byref(cam), ptr(point_image), H, W, byref(prm), ptr(code), ptr(tgt),
+         ptr(warped), ptr(midx), ptr(src_o), ptr(tgt_o), ptr(a_o), ptr(w_o), ptr(count), _stream(points))
+    return code, tgt, warped, midx, src_o, tgt_o, a_o, w_o, count
+
+
+@associate.register_fake
+def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, point_image, intr, dist_max, cos_min,
+      edge_max, target_mode, max_matches):
+    P, M = points.shape[0], int(max_matches)
+    f, i = torch.float32, torch.int32
+    return (points.new_empty((P,), dtype=torch.uint8), points.new_empty((P, 3), dtype=f),
+            points.new_empty((P, 3), dtype=f), points.new_empty((M,), dtype=i), points.new_empty((M, 3), dtype=f),
+            points.new_empty((M, 3), dtype=f), points.new_empty((M, 4), dtype=i), points.new_empty((M, 4), dtype=f),
+            points.new_empty((2,), dtype=i))
+
+
 # --------------------------------------------------------------------------------------------- dense SPD solve
 @_op("spd_solve", mutates_args=())
 def spd_solve(A: Tensor, b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
@@ -369,4 +414,4 @@ def _(state, handle, n_nodes, num_iter):
 
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
-       "gn_linearize", "gn_step", "gn_finish", "spd_solve")
+       "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate")

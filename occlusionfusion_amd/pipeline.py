@@ -144,3 +144,28 @@ class FusionPipeline:
         self.last = self.solve(fi, next_fi)
         self.integrate(fi, t, count_updates)
         return self.last
+
+    def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, **assoc):
+        """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
+        by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
+        icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
+        unless motion=False), then integrated. **assoc: dist_max, cos_min, edge_max, mode, max_matches (default: the
+        pipeline's n_matches). The result carries "assoc": per ICP iteration the accepted / emitted counts and the code
+        histogram."""
+        from .association import ProjectiveAssociator, icp_track
+        if getattr(self, "_track", None) is None:
+            pts = torch.from_numpy(np.ascontiguousarray(self.seq.canonical_points, np.float32)).to(self.device)
+            a, w, v = self.wf.skin_device(pts)
+            self._track = (pts, a, w, v, ProjectiveAssociator(pts.shape[0], self.device))
+        pts, a, w, v, assoc_h = self._track
+        assoc.setdefault("max_matches", self.n_matches)
+        self.vol.stage(fi.im)
+        out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
+                                fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
+                                (fi.tpos, fi.conf) if motion else None, icp_iters,
+                                **assoc)
+        out["assoc"] = log
+        self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
+        self.last = out
+        self.integrate(fi, t, count_updates)
+        return out
