@@ -40,6 +40,9 @@
  *                           twin: the reference's matches come from learned front-ends; its geometric fallback is the
  *                           truncated chamfer term, NonRigidICP/model/loss.py:275-292. Parity unpinned, as for ofx_raycast;
  *                           restated op for op by tests/assoc_ref.py)
+ *   ofx_surface_*           (new) skinned surface points of the TSDF, the tracking model — (no reference twin: the
+ *                           reference re-meshes and re-skins per frame, tsdf.get_deformed_model / optimizer.update in
+ *                           fusion_tests/lepard_nicp_test.py:471,537. Parity unpinned; restated by tests/surface_ref.py)
  *   ofx_depth_to_pc         Registration.optimize target cloud: depth_2_pc, NonRigidICP/model/geometry.py:44-59,
  *                           mask compaction, map_pixel_to_pcd              registration_fusion.py:104-109,388-395
  *   ofx_pixel_anchors_euclidean  csrc compute_pixel_anchors_euclidean     csrc/cpu/graph_proc.cpp:610-709
@@ -345,6 +348,52 @@ int ofx_associate(void* handle, const float* points, const float* normals, const
                   const ofx_assoc_params* prm, uint8_t* code, float* tgt, float* warped, int32_t* match_idx,
                   float* src_out, float* tgt_out, int32_t* anchors_out, float* weights_out, int32_t* count,
                   ofx_stream_t s);
+
+/* ---------------- Skinned surface points of the TSDF (new capability; the reference has none — parity unpinned) ----------------
+ * The tracking model read off the volume itself: canonical surface points, their outward normals and their anchors and
+ * weights, in one pass over the skin cache's listed bricks — what the reference gets per frame from marching cubes plus a
+ * k-NN skin of the vertices (tsdf.get_deformed_model / optimizer.update, fusion_tests/lepard_nicp_test.py:471,537). A
+ * point's skin is the cached skin of its voxel, the one ofx_integrate* warps that voxel with, so the tracked and the
+ * fused model move identically. Restated op for op by tests/surface_ref.py.
+ * Inputs: the bricked tsdf and weight of a WHOLE volume (a shard, brick_x0 != 0 || brick_x1 != ceil(Dx/8), is
+ * OFX_ERR_ARG; so are volumes of 2^31 voxels or more), and the skin cache as ofx_skin_volume writes it: brick_list
+ * int32[n_list], skin_anchors u16[n_list*512*4] (0xFFFF = none), skin_weights f32[n_list*512*4], k == 4 (else OFX_ERR_ARG).
+ * Every voxel v = (i, j, k) of every listed brick gets the first code that applies (comparisons written so that NaN fails):
+ *   1  brick padding (i >= Dx etc.) or the volume's boundary layer (an index is 0 or dim - 1)
+ *   2  !(weight[v] >= w_min)
+ *   3  !(phi >= 0 && phi < 1), phi = tsdf[v]: not in front of the surface inside the truncation band
+ *   4  one of the six face neighbours has !(weight >= w_min)
+ *   5  no face neighbour has phi_n < 0: not next to the zero level
+ *   6  degenerate gradient: g_a = phi(+e_a) - phi(-e_a), l2 = (g_x^2 + g_y^2) + g_z^2, len = f32(sqrt(f64(l2))); rejected
+ *      if !(l2 > 0), l2 not finite, or phi > len (a Newton step longer than two voxels)
+ *   7  skin-invalid: one of its four cached anchors is 0xFFFF (last: only geometric survivors touch the skin cache)
+ *   0  accepted
+ * Accepted voxel (f32, no contraction, every step fixed):
+ *   c_a = f32(f64(origin_a) + voxel_size*f64(i_a))   the voxel position as the integrate kernels form it
+ *   n_a = g_a / len, correctly rounded               unit normal towards increasing tsdf (the camera side: the sense of
+ *                                                     ofx_mesh_emit's normals, and what ofx_associate expects)
+ *   t   = (phi * f32(2*voxel_size)) / len            product rounded to f32, division correctly rounded
+ *   p_a = c_a - n_a*t
+ *   anchors = the four cached anchors widened to int32, weights = the four cached weights,
+ *   voxel = the C-order index (i*Dy + j)*Dz + k
+ * Rows: ascending (list slot, in-brick voxel l = (lx*8 + ly)*8 + lz). With n accepted: all are emitted if n <= max_points;
+ * otherwise the accepted voxel of rank r is emitted iff floor((r+1)*max_points/n) > floor(r*max_points/n) (64-bit integers;
+ * ofx_associate's rule). count (DEVICE int32[2]) = [accepted, emitted]. Outputs, max_points rows each: points f32[.,3],
+ * normals f32[.,3], anchors i32[.,4], weights f32[.,4] (both 16-byte aligned), voxel i32[.], valid u8[.]. Emitted rows
+ * have valid = 1; rows from `emitted` to max_points are defined too — valid = 0, voxel = -1, zero points / normals /
+ * anchors / weights — so the padded arrays go to ofx_associate without a host read-back. code (may be NULL): u8[n_list*512]
+ * in (slot, l) order. n_list == 0 is legal: count = [0, 0], every row padding. n_list above the handle's max_bricks is
+ * OFX_ERR_ARG. A list entry that is no brick of the volume gives code 1 for its 512 voxels and reads nothing; a brick
+ * listed twice is sampled twice (each slot with its own cached skin). Stream-ordered: no allocation and no host sync inside the call; the handle owns the per-brick counts,
+ * their scan and the accepted-voxel bit words. Order comes from counts and a scan, never from atomics: two calls give the
+ * same bytes. */
+int ofx_surface_create(int32_t max_bricks, void** handle);
+int ofx_surface_destroy(void* handle);
+int ofx_surface_points(void* handle, const ofx_volume_desc* desc, const float* tsdf, const float* weight,
+                       const int32_t* brick_list, int32_t n_list, const uint16_t* skin_anchors,
+                       const float* skin_weights, int32_t k, float w_min, int32_t max_points, float* points,
+                       float* normals, int32_t* anchors, float* weights, int32_t* voxel, uint8_t* valid, uint8_t* code,
+                       int32_t* count, ofx_stream_t s);
 
 /* ---------------- Standalone skinning / anchors ---------------- */
 /* csrc twins, exact (Eigen summation order, list tie order, f32 weights): outputs (H, W, 4) images,

@@ -9,7 +9,7 @@ _EXPORTS = {
     "TSDFVolume": "tsdf", "volume_geometry": "tsdf", "shard_bricks": "sharding", "match_range": "sharding",
     "WarpField": "warpfield", "EDGraph": "warpfield",
     "GaussNewtonSolver": "registration", "Registration": "registration", "spd_solve": "registration",
-    "FusionPipeline": "pipeline", "ProjectiveAssociator": "association",
+    "FusionPipeline": "pipeline", "ProjectiveAssociator": "association", "SurfaceSampler": "surface",
     "backproject_depth": "image_proc", "compute_mesh_from_depth": "image_proc", "depth_2_pc": "image_proc",
 }
 

@@ -91,6 +91,9 @@ _SIGS = {
     "ofx_assoc_create": [c_int64, P],
     "ofx_assoc_destroy": [P],
     "ofx_associate": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P],
+    "ofx_surface_create": [c_int32, P],
+    "ofx_surface_destroy": [P],
+    "ofx_surface_points": [P, P, P, P, P, c_int32, P, P, c_int32, c_float, c_int32, P, P, P, P, P, P, P, P, P],
     "ofx_pixel_anchors_euclidean": [P, c_int32, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_pixel_anchors_geodesic": [P, P, c_int32, c_int64, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_remap_anchors": [P, c_int64, P, c_int32, P, P],

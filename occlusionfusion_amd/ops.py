@@ -234,6 +234,53 @@ def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, poi
             points.new_empty((2,), dtype=i))
 
 
+# --------------------------------------------------------------------------------------------- surface points
+@_op("surface_points", mutates_args=("state", "points", "normals", "anchors_out", "weights_out", "voxel", "valid", "code",
+                                     "count"))
+def surface_points(state: Tensor, handle: int, tsdf: Tensor, weight: Tensor, brick_list: Tensor, n_list: int,
+                   skin_anchors: Tensor, skin_weights: Tensor, k: int, dims: List[int], origin: List[float],
+                   voxel_size: float, trunc_margin: float, w_min: float, points: Tensor, normals: Tensor,
+                   anchors_out: Tensor, weights_out: Tensor, voxel: Tensor, valid: Tensor, code: Optional[Tensor],
+                   count: Tensor) -> None:
+    """ofx_surface_points (new capability, no reference twin): the skinned surface points of a whole bricked volume
+    (tsdf / weight) read through its skin cache (brick_list, n_list, skin_anchors u16 in int16 storage, skin_weights,
+    k = 4), written into the caller's max_points-row outputs: points / normals f32 (M,3), anchors_out i32 (M,4),
+    weights_out f32 (M,4), voxel i32 (M,), valid u8 (M,), code u8 (n_list*512,) or None, count i32 (2,) = [accepted,
+    emitted] on the device. Rows past `emitted` are defined padding (valid 0, voxel -1, zeros). `handle` is an
+    ofx_surface_create handle sized for at least n_list bricks; `state` is its ordering token."""
+    M = points.shape[0]
+    nbx = (int(dims[0]) + 7) // 8
+    desc = _volume_desc(dims, [0, nbx], origin, voxel_size, trunc_margin, 0)
+    if code is not None and code.shape[0] < int(n_list) * 512:
+        raise ValueError(f"surface_points: code holds {code.shape[0]} entries, {int(n_list) * 512} are needed")
+    for name, t, rows in (("normals", normals, 3), ("anchors_out", anchors_out, 4), ("weights_out", weights_out, 4)):
+        if t.shape[0] != M or t.shape[1] != rows:
+            raise ValueError(f"surface_points: {name} must be ({M}, {rows}), got {tuple(t.shape)}")
+    if voxel.shape[0] != M or valid.shape[0] != M or count.shape[0] != 2:
+        raise ValueError("surface_points: voxel / valid must have max_points rows and count two entries")
+    call("ofx_surface_points", _lib.c_void_p(handle), byref(desc), ptr(tsdf), ptr(weight), ptr(brick_list), int(n_list),
+         ptr(skin_anchors), ptr(skin_weights), int(k), float(w_min), M, ptr(points), ptr(normals), ptr(anchors_out),
+         ptr(weights_out), ptr(voxel), ptr(valid), ptr(code), ptr(count), _stream(tsdf))
+
+
+@surface_points.register_fake
+def _(state, handle, tsdf, weight, brick_list, n_list, skin_anchors, skin_weights, k, dims, origin, voxel_size,
+      trunc_margin, w_min, points, normals, anchors_out, weights_out, voxel, valid, code, count):
+    return None
+
+
+def surface_outputs(max_points, device, n_list=None):
+    """Output tensors of torch.ops.ofx.surface_points for max_points rows (code for n_list bricks, None without):
+    (points, normals, anchors, weights, voxel, valid, code, count)."""
+    M = int(max_points)
+    f, i = torch.float32, torch.int32
+    return (torch.empty((M, 3), dtype=f, device=device), torch.empty((M, 3), dtype=f, device=device),
+            torch.empty((M, 4), dtype=i, device=device), torch.empty((M, 4), dtype=f, device=device),
+            torch.empty(M, dtype=i, device=device), torch.empty(M, dtype=torch.uint8, device=device),
+            None if n_list is None else torch.empty(max(1, int(n_list)) * 512, dtype=torch.uint8, device=device),
+            torch.empty(2, dtype=i, device=device))
+
+
 # --------------------------------------------------------------------------------------------- dense SPD solve
 @_op("spd_solve", mutates_args=())
 def spd_solve(A: Tensor, b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
@@ -414,4 +461,4 @@ def _(state, handle, n_nodes, num_iter):
 
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
-       "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate")
+       "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points")

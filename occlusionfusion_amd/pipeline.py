@@ -55,6 +55,8 @@ class FusionPipeline:
         # a caller reading the volume synchronises the device, not only its own stream)
         self.overlap = overlap
         self.int_stream = None
+        self._vmodel = None       # track_step(model="volume"): the last sampled volume model (padded device arrays)
+        self.model_counts = []    # ... and each sampling's device [accepted, emitted]
 
     def prepare(self, t):
         """Host-side synthetic inputs of frame t -> device (outside any timed region)."""
@@ -145,13 +147,69 @@ class FusionPipeline:
         self.integrate(fi, t, count_updates)
         return self.last
 
-    def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, **assoc):
+    def sample_model(self, max_model_points, w_min=1.0):
+        """(Re)sample the volume model on torch's current stream (WarpField.surface_points, sync=False: no host read):
+        max_model_points padded rows and their valid mask. model_counts keeps a device copy of every sampling's
+        [accepted, emitted] (read them at the end of a run, not per frame)."""
+        m = self.wf.surface_points(int(max_model_points), w_min, sync=False)
+        self._vmodel = m
+        self.model_counts.append(m["count"].clone())
+        return m
+
+    def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, assoc):
+        from .association import ProjectiveAssociator, icp_track
+        M = int(max_model_points)
+        if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
+            self._vassoc = ProjectiveAssociator(M, self.device)
+        if getattr(self, "_vmodel", None) is None or self._vmodel["points"].shape[0] != M:
+            self.flush()
+            if self.int_stream is not None:   # (an overlapped integrate of an earlier step() may still be running)
+                torch.cuda.current_stream(self.device).wait_stream(self.int_stream)
+            self.model_counts = []
+            self.sample_model(M, w_min)       # the volume as integrate_source (or the frames so far) left it
+        m = self._vmodel
+        assoc.setdefault("max_matches", self.n_matches)
+        self.vol.stage(fi.im)
+        out, log, _ = icp_track(self._vassoc, self.solver, self.nodes_t, self.edges_t, self.ew_t, m["points"],
+                                m["normals"], m["anchors"], m["weights"], m["valid"], fi.im[-1], self.intr,
+                                self.prev_rot, self.prev_trans, (fi.tpos, fi.conf) if motion else None, icp_iters,
+                                **assoc)
+        out["assoc"] = log
+        self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
+        self.last = out
+        # integrate, then re-sample in the integrate's stream order; the next association reads the refreshed model, so
+        # an overlapped integrate is enqueued now (flush) and this stream waits for it: no integrate / solve overlap here
+        done = torch.cuda.Event()
+
+        def resample():
+            self.sample_model(M, w_min)
+            done.record()
+        self.integrate(fi, t, count_updates, after=resample)
+        self.flush()
+        torch.cuda.current_stream(self.device).wait_event(done)
+        return out
+
+    def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
+                   max_model_points=65536, w_min=1.0, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
         unless motion=False), then integrated. **assoc: dist_max, cos_min, edge_max, mode, max_matches (default: the
         pipeline's n_matches). The result carries "assoc": per ICP iteration the accepted / emitted counts and the code
-        histogram."""
+        histogram.
+
+        model="volume": the tracked model is the fused volume itself instead of seq.canonical_points — surface points
+        sampled from the TSDF with their voxels' cached skin and their normals (WarpField.surface_points: at most
+        max_model_points rows, voxels observed with weight >= w_min), sampled once from the volume as integrate_source
+        left it and again after every integrate, so that newly fused surface becomes a tracking target; a depth stream
+        alone then drives the loop. The padded arrays and their valid mask go to the association as they are (no host
+        read for the model; model_counts holds each sampling's device [accepted, emitted]). The re-sampling follows the
+        integrate in its stream order and the next association waits for it: with overlap=True the pending integrate is
+        enqueued at once (flush()), so the integrate / solve overlap does not apply in this mode."""
+        if model == "volume":
+            return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, assoc)
+        if model != "canonical":
+            raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
         if getattr(self, "_track", None) is None:
             pts = torch.from_numpy(np.ascontiguousarray(self.seq.canonical_points, np.float32)).to(self.device)

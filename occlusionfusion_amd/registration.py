@@ -448,6 +448,26 @@ class Registration:
         self.source_pcd = vt[v]
         self.point_anchors = a[v]
         self.anchor_weight = w[v]
+        self.source_normals = None   # (set by update_from_volume only: caller-given vertices carry no normals)
+
+    def update_from_volume(self, max_points=None, w_min=1.0):
+        """The model from the fused volume instead of caller-given vertices (the reference's per-frame
+        optimizer.update(tsdf.get_canonical_model()[0]), fusion_tests/lepard_nicp_test.py:537, without the mesh and
+        the k-NN skin): WarpField.surface_points — surface voxels of the TSDF observed with weight >= w_min, with the
+        skin the integrate warps them with — becomes source_pcd / point_anchors / anchor_weight, every point valid, and
+        source_normals holds their unit normals, which track() then gates with. max_points: None keeps every accepted
+        voxel (one more host read to size the arrays), else they are thinned evenly to at most that many. Needs the
+        warp field's skin cache (skin_tsdf_cache()). -> the number of model points."""
+        wf = self.warpfield
+        if max_points is None:
+            max_points = wf.surface_points(0, w_min)["accepted"]
+        m = wf.surface_points(int(max_points), w_min)
+        self.source_pcd = m["points"].clone()
+        self.point_anchors = m["anchors"].clone()
+        self.anchor_weight = m["weights"].clone()
+        self.source_normals = m["normals"].clone()
+        self.valid_source_verts = np.ones(m["emitted"], bool)
+        return m["emitted"]
 
     def _intr4(self):
         K = self.intrinsics
@@ -488,7 +508,8 @@ class Registration:
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
         projective association (association.ProjectiveAssociator, ofx_associate) of source_pcd under the current
         prev_rot / prev_trans, and a GN solve on the emitted matches from that estimate. source_normals: unit normals of
-        the canonical vertices given to update() (all of them, or the valid ones only), or None (no normal gate).
+        the canonical vertices given to update() (all of them, or the valid ones only), or None (no normal gate; after
+        update_from_volume(): the volume model's own normals).
         **assoc: dist_max, cos_min, edge_max, mode ("plane" / "point"), max_matches. Without motion data the motion
         rows vanish (nodes as targets, confidence 0). Raises association.TooFewMatches, with no solve launched, if an
         association emits fewer than 4·K = 16 matches. Returns optimize's result dict (frame ids: None and the
@@ -500,7 +521,7 @@ class Registration:
         P = self.source_pcd.shape[0]
         if getattr(self, "_assoc", None) is None or self._assoc.max_points < P:
             self._assoc = ProjectiveAssociator(P, self.device)
-        nrm = None
+        nrm = getattr(self, "source_normals", None)   # a model from the volume (update_from_volume) brings its normals
         if source_normals is not None:
             nrm = torch.as_tensor(np.ascontiguousarray(source_normals, np.float32), device=self.device).reshape(-1, 3)
             if nrm.shape[0] != P:

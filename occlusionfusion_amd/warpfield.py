@@ -448,6 +448,44 @@ class WarpField:
              c.k, ptr(a), ptr(w), ptr(v), stream_ptr())
         return a.cpu().numpy(), w.cpu().numpy(), v.cpu().numpy().astype(bool)
 
+    def surface_points(self, max_points, w_min=1.0, with_codes=False, sync=True):
+        """Canonical surface points of the fused volume with the skin the integrate warps them with (surface.
+        SurfaceSampler, ofx_surface_points; no reference twin — the reference re-meshes and re-skins every frame):
+        voxels just in front of the zero level, observed with weight >= w_min like their six face neighbours, each
+        moved onto the surface by one Newton step along its central-difference gradient. -> dict(points, normals (unit,
+        towards the camera side), anchors i32 (.,4), weights (.,4), voxel (C-order voxel index), valid u8), in
+        ascending (cache brick, in-brick voxel) order; more than max_points accepted voxels are thinned evenly by rank.
+
+        sync=True reads the counts back (one host synchronisation): the arrays are sliced to `emitted`, and
+        "accepted" / "emitted" and, with with_codes, "code" (u8 per voxel of the listed bricks) and "histogram" (counts
+        per code, surface.CODE_NAMES) are host values. sync=False does no host read: the arrays keep their max_points
+        rows — rows past the emitted count are defined padding (valid 0, voxel -1, zeros) that ProjectiveAssociator.
+        associate takes as they are — and "count" is the device int32[2] = [accepted, emitted]. The arrays belong to
+        the warp field's sampler: the next call with the same max_points overwrites them.
+
+        Raises if no skin cache has been built (skin_tsdf_cache()), or for a sharded volume."""
+        from .surface import CODE_NAMES, SurfaceSampler
+        if self._cache is None:
+            raise RuntimeError("surface_points needs the skin cache: call skin_tsdf_cache() first")
+        c = self._cache
+        sm = getattr(self, "_sampler", None)
+        if sm is None or sm.max_bricks < c.n_list:
+            sm = self._sampler = SurfaceSampler(max(1, c.n_list), self.device)
+        out = sm.sample(self.tsdf, c, max_points, w_min, with_codes)
+        if not sync:
+            return out
+        if with_codes:
+            hist = torch.bincount(out["code"].to(torch.int64), minlength=len(CODE_NAMES))
+            host = torch.cat([out["count"].to(torch.int64), hist]).cpu().tolist()   # the one host sync
+        else:
+            host = out["count"].cpu().tolist()
+        n_acc, n_emit = int(host[0]), int(host[1])
+        res = {k: out[k][:n_emit] for k in ("points", "normals", "anchors", "weights", "voxel", "valid")}
+        res.update(accepted=n_acc, emitted=n_emit, count=out["count"], code=out["code"])
+        if with_codes:
+            res["histogram"] = [int(x) for x in host[2:2 + len(CODE_NAMES)]]
+        return res
+
     # ------------------------------------------------------------------ deformation
     def deform_device(self, points, anchors, weights, valid=None, normals=False):
         pts = _t(points, self.device, torch.float32).reshape(-1, 3)
