@@ -349,6 +349,44 @@ int ofx_associate(void* handle, const float* points, const float* normals, const
                   float* src_out, float* tgt_out, int32_t* anchors_out, float* weights_out, int32_t* count,
                   ofx_stream_t s);
 
+/* ---------------- Rigid pre-alignment: point-to-plane ICP (new capability; the reference has none — parity unpinned) -------
+ * The cheap stage in front of the non-rigid solve: a rigid pose [R|t] (6 unknowns) that brings ALL model points, warped by
+ * the current node transforms, onto the depth frame. Inputs and their checks are ofx_associate's. pose is DEVICE f64[12],
+ * row-major [R|t], read and written in place. Restated op for op by tests/rigid_ref.py. One iteration, per point (f32, no
+ * contraction, every step fixed):
+ *   x', n' = ofx_associate's warped point and normalised warped normal (the same device code)
+ *   Rf, tf = the f32 roundings of the pose; y_a = ((Rf_a0*x' + Rf_a1*y') + Rf_a2*z') + tf_a; m = Rf n' in the same order,
+ *            not renormalised
+ *   pixel, q, n_q and the codes 1-6 are ofx_associate's, with y and m in place of x' and n'
+ *   accepted: e = q - y, r = (e.n_q summed (x + y) + z), c = y x n_q (a*b - c*d per component), row J = [c, n_q]
+ * Reduction in f64: A = sum J^T J (21 upper entries), b = sum J^T r, sum r^2 and the accepted count. Every term is a product
+ * of two f32 values (exact in f64); only the sums round. No atomics: cross-lane shuffles per wave, LDS per workgroup, one
+ * record per workgroup, the records summed in a fixed order; the grid depends on n_points alone, so two calls and two
+ * handles give the same bytes.
+ * Solve (f64): A += damping*trace(A)/6*I, 6x6 Cholesky, xi = (omega, v) = A^-1 b, dR = exp(omega) (Rodrigues, series for
+ * |omega| < 1e-8), pose <- [dR R | dR t + v].
+ * systems (DEVICE f64[iters][32]), row i of iteration i: [0..20] A row-major upper, undamped; [21..26] b; [27] sum r^2;
+ * [28] accepted count; [29] status — 0 solved, 1 fewer than min_matches accepted, 2 a non-positive pivot (or a non-finite
+ * step), 3 drained: after an iteration that converged (|omega| and |v| both below stop_twist; that iteration's step is
+ * applied) or that had a non-zero status; [30] |omega|; [31] |v|. A non-zero status leaves the pose as it is; a drained row
+ * is status 3 and zeros. code (may be NULL): u8[P], the codes of the last iteration that ran.
+ * Stream-ordered: all iterations are enqueued at once (two launches each), no allocation and no host sync inside; the handle
+ * owns the workgroup records, sized at create for max_points (n_points above it is OFX_ERR_ARG). n_points = 0 is legal: status
+ * 1 in every row, pose untouched. */
+typedef struct ofx_rigid_params {
+  float dist_max, cos_min, edge_max;   /* ofx_associate's gates, same meaning */
+  int32_t iters;                       /* >= 1 */
+  int32_t min_matches;                 /* fewer accepted points: status 1, pose kept (default 6) */
+  double damping;                      /* relative: A += damping * trace(A)/6 * I (default 1e-6) */
+  double stop_twist;                   /* |omega| and |v| both below it: converged, later iterations drain (0 = never) */
+} ofx_rigid_params;
+int ofx_rigid_create(int64_t max_points, void** handle);
+int ofx_rigid_destroy(void* handle);
+int ofx_rigid_icp(void* handle, const float* points, const float* normals, const int32_t* anchors, const float* weights,
+                  const uint8_t* valid, int64_t n_points, const float* packed_nodes, int32_t n_nodes,
+                  const ofx_camera* cam, const float* point_image, int32_t height, int32_t width,
+                  const ofx_rigid_params* prm, double* pose, uint8_t* code, double* systems, ofx_stream_t s);
+
 /* ---------------- Skinned surface points of the TSDF (new capability; the reference has none — parity unpinned) ----------------
  * The tracking model read off the volume itself: canonical surface points, their outward normals and their anchors and
  * weights, in one pass over the skin cache's listed bricks — what the reference gets per frame from marching cubes plus a

@@ -31,6 +31,11 @@ class AssocParams(ctypes.Structure):
                 ("max_matches", c_int32), ("_pad", c_int32)]
 
 
+class RigidParams(ctypes.Structure):
+    _fields_ = [("dist_max", c_float), ("cos_min", c_float), ("edge_max", c_float), ("iters", c_int32),
+                ("min_matches", c_int32), ("damping", c_double), ("stop_twist", c_double)]
+
+
 class GnParams(ctypes.Structure):
     _fields_ = [("num_iter", c_int32), ("use_edge_weighting", c_int32), ("pcg_max_iter", c_int32), ("pcg_warm", c_int32),
                 ("lambda_flow", c_double), ("lambda_depth", c_double), ("lambda_arap", c_double),
@@ -91,6 +96,9 @@ _SIGS = {
     "ofx_assoc_create": [c_int64, P],
     "ofx_assoc_destroy": [P],
     "ofx_associate": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P],
+    "ofx_rigid_create": [c_int64, P],
+    "ofx_rigid_destroy": [P],
+    "ofx_rigid_icp": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P],
     "ofx_surface_create": [c_int32, P],
     "ofx_surface_destroy": [P],
     "ofx_surface_points": [P, P, P, P, P, c_int32, P, P, c_int32, c_float, c_int32, P, P, P, P, P, P, P, P, P],

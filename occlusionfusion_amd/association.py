@@ -6,7 +6,8 @@ with the current estimate, look them up in the target depth frame's vertex map, 
 normals, and hand the surviving pairs to GaussNewtonSolver.optimize (torch.ops.ofx.associate -> ofx_associate, one gather
 kernel + an ordered compaction). It has no reference twin; its geometric relative there is the truncated chamfer term
 (NonRigidICP/model/loss.py:275-292). icp_track is the loop around it that Registration.track and
-FusionPipeline.track_step share. This is the data term for what the camera sees: motion of occluded nodes still needs the
+FusionPipeline.track_step share; RigidAligner (torch.ops.ofx.rigid_icp -> ofx_rigid_icp) is its optional first stage, a
+rigid point-to-plane ICP of all model points whose pose fold_rigid folds into the node transforms. This is the data term for what the camera sees: motion of occluded nodes still needs the
 motion-completion input.
 """
 import numpy as np
@@ -108,16 +109,123 @@ class ProjectiveAssociator:
         return self.last
 
 
+class RigidAligner:
+    """Owns an ofx_rigid handle (the workgroup records of the reduction for up to max_points points): the rigid,
+    6-unknown point-to-plane ICP in front of the non-rigid solve (torch.ops.ofx.rigid_icp -> ofx_rigid_icp)."""
+
+    def __init__(self, max_points, device=None):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.max_points = int(max_points)
+        self._h = _lib.c_void_p()
+        with torch.cuda.device(self.device):
+            call("ofx_rigid_create", self.max_points, byref(self._h))
+        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)   # ofx::rigid_icp ordering token
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.lib.ofx_rigid_destroy(h)
+            except Exception:
+                pass
+        self._h = None
+
+    def align(self, points, normals, anchors, weights, valid, warpfield_or_packed_nodes, point_image, intr, pose=None,
+              iters=4, dist_max=0.05, cos_min=0.5, edge_max=0.03, damping=1e-6, min_matches=6, stop_twist=0.0,
+              sync=False):
+        """iters point-to-plane iterations of all the points (inputs as ProjectiveAssociator.associate) from pose — a
+        (3,4) [R|t], None = the identity; never modified — under the transforms of a WarpField or of a packed (N,16) node
+        tensor. Returns dict(pose (3,4) f64 on the device, systems (iters,32) f64, code u8 (P,)); the layout of a systems
+        row is ofx_rigid_icp's. Everything is enqueued on torch's current stream and nothing is read back, unless
+        sync=True: then pose_host / systems_host (numpy) and the per-iteration lists accepted / rms (sqrt(Σr²/count),
+        nan without matches) / status are added, at the cost of one host synchronisation."""
+        d = self.device
+        pts = _f32(points, d, (-1, 3))
+        P = pts.shape[0]
+        if P > self.max_points:
+            raise ValueError(f"{P} points exceed the aligner's capacity ({self.max_points})")
+        packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
+                  else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
+        a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
+        a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
+        v = None
+        if valid is not None:
+            v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
+            v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
+        vm = _f32(point_image, d)
+        assert vm.dim() == 3 and vm.shape[0] == 3, "point image must be (3, H, W)"
+        if pose is None:
+            p = torch.eye(3, 4, dtype=torch.float64, device=d)
+        else:
+            p = pose if isinstance(pose, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(pose, np.float64))
+            p = p.to(device=d, dtype=torch.float64).reshape(3, 4).clone().contiguous()
+        code, systems = torch.ops.ofx.rigid_icp(self._state, self._h.value, pts, _f32(normals, d, (P, 3)), a,
+                                                _f32(weights, d, (P, 4)), v, packed, vm, [float(x) for x in intr[:4]],
+                                                float(dist_max), float(cos_min), float(edge_max), int(iters),
+                                                int(min_matches), float(damping), float(stop_twist), p)
+        out = {"pose": p, "systems": systems, "code": code}
+        if sync:
+            host = torch.cat([p.reshape(-1), systems.reshape(-1)]).cpu().numpy()   # the one host sync
+            sys_h = host[12:].reshape(-1, 32)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rms = np.sqrt(sys_h[:, 27] / sys_h[:, 28])
+            out.update(pose_host=host[:12].reshape(3, 4), systems_host=sys_h,
+                       accepted=[int(x) for x in sys_h[:, 28]], rms=[float(x) for x in rms],
+                       status=[int(x) for x in sys_h[:, 29]])
+        return out
+
+
+def fold_rigid(nodes, rot, trans, pose):
+    """Fold a rigid pose [R|t] (3,4) into the node transforms: R_k' = R·R_k, T_k' = R·(g_k + T_k) + t − g_k, computed in
+    f64 on the pose's device and rounded once to f32; rot / trans None = the identity. The ED warp of any point then
+    becomes R·warp(x) + S·t (S: the sum of its skin weights), so nothing downstream needs a notion of a camera pose.
+    -> (rot' (N,3,3) f32, trans' (N,3) f32) device tensors. No host read."""
+    p = pose if isinstance(pose, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(pose, np.float64))
+    p = p.to(dtype=torch.float64).reshape(3, 4)
+    d = p.device
+    g = (nodes if isinstance(nodes, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(nodes)))
+    g = g.to(device=d, dtype=torch.float64).reshape(-1, 3)
+    N = g.shape[0]
+    R, t = p[:, :3], p[:, 3]
+    if rot is None:
+        Rk = torch.eye(3, dtype=torch.float64, device=d).expand(N, 3, 3)
+    else:
+        Rk = (rot if isinstance(rot, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(rot)))
+        Rk = Rk.to(device=d, dtype=torch.float64).reshape(N, 3, 3)
+    gt = g
+    if trans is not None:
+        Tk = (trans if isinstance(trans, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(trans)))
+        gt = g + Tk.to(device=d, dtype=torch.float64).reshape(N, 3)
+    # explicit sums (j ascending) rather than a BLAS call: the order is fixed
+    Rn = (R[None, :, 0, None] * Rk[:, None, 0, :] + R[None, :, 1, None] * Rk[:, None, 1, :]) \
+        + R[None, :, 2, None] * Rk[:, None, 2, :]
+    Tn = (((R[None, :, 0] * gt[:, 0, None] + R[None, :, 1] * gt[:, 1, None]) + R[None, :, 2] * gt[:, 2, None])
+          + t[None, :]) - g
+    return Rn.to(torch.float32).contiguous(), Tn.to(torch.float32).contiguous()
+
+
 def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
-              valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3, **assoc):
+              valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3,
+              rigid_iters=0, rigid=None, **assoc):
     """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
     associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
     matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
     0, so the motion rows vanish. An association that emits fewer than 4·K = 16 matches raises TooFewMatches before any
-    solve. -> (the last optimize result, [per iteration dict(accepted, emitted, histogram)], vertex map)."""
+    solve. -> (the last optimize result, [per iteration dict(accepted, emitted, histogram)], vertex map).
+
+    rigid_iters > 0 puts the rigid stage in front: before the first association, rigid_iters point-to-plane iterations
+    of all the points (rigid: a RigidAligner, required then) from the identity pose around the current estimate, with
+    the association's gates; the pose is folded into the estimate (fold_rigid) and the loop goes on from there. The
+    stage reads nothing back: a failed rigid stage folds an unchanged pose. The result then gains "rigid": dict(pose,
+    systems), device tensors."""
     from .image_proc import backproject_depth_device
+    rigid_iters = int(rigid_iters)
+    if rigid_iters < 0:
+        raise ValueError("rigid_iters must not be negative")
     if int(icp_iters) < 1:
         raise ValueError("icp_iters must be at least 1")
+    if rigid_iters > 0 and rigid is None:
+        raise ValueError("rigid_iters > 0 needs a RigidAligner (rigid=...)")
     d = solver.device
     prm = dict(ASSOC_DEFAULTS)
     unknown = set(assoc) - set(prm)
@@ -131,6 +239,13 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     vm = backproject_depth_device(dep.to(device=d, dtype=torch.float32), fx, fy, cx, cy)
     tloc, tconf = complete_node_motion_data if complete_node_motion_data is not None else (None, None)
     rot, trans, out, log = prev_rot, prev_trans, None, []
+    rig = None
+    if rigid_iters > 0:
+        gates = {k: prm[k] for k in ("dist_max", "cos_min", "edge_max")}
+        r = rigid.align(points, normals, anchors, weights, valid, pack_transforms(graph_nodes, rot, trans, d), vm,
+                        (fx, fy, cx, cy), pose=None, iters=rigid_iters, **gates)
+        rot, trans = fold_rigid(graph_nodes, rot, trans, r["pose"])
+        rig = {"pose": r["pose"], "systems": r["systems"]}
     for it in range(int(icp_iters)):
         m = associator.associate(points, normals, anchors, weights, valid, pack_transforms(graph_nodes, rot, trans, d),
                                  vm, (fx, fy, cx, cy), **prm)
@@ -141,4 +256,6 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         out = solver.optimize(graph_nodes, graph_edges, graph_edges_weights, tloc, tconf, m["src"], m["anchors"],
                               m["weights"], m["tgt"], (fx, fy, cx, cy), prev_rot=rot, prev_trans=trans)
         rot, trans = out["node_rotations"], out["node_translations"]
+    if rig is not None:
+        out["rigid"] = rig
     return out, log, vm

@@ -234,6 +234,42 @@ def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, poi
             points.new_empty((2,), dtype=i))
 
 
+# --------------------------------------------------------------------------------------------- rigid pre-alignment
+@_op("rigid_icp", mutates_args=("state", "pose"))
+def rigid_icp(state: Tensor, handle: int, points: Tensor, normals: Optional[Tensor], anchors: Tensor, weights: Tensor,
+              valid: Optional[Tensor], packed_nodes: Tensor, point_image: Tensor, intr: List[float], dist_max: float,
+              cos_min: float, edge_max: float, iters: int, min_matches: int, damping: float, stop_twist: float,
+              pose: Tensor) -> Tuple[Tensor, Tensor]:
+    """ofx_rigid_icp (new capability, no reference twin): `iters` point-to-plane ICP iterations of all the points (P,3)
+    — skinned and warped as in `associate`, then moved by pose — against the vertex map point_image (3,H,W), with
+    associate's gates. pose: f64 (3,4) [R|t] on the device, updated in place. -> code u8 (P,) of the last iteration that
+    ran, systems f64 (iters, 32): per iteration the 21 upper entries of A, b, Σr², the accepted count, the status (0
+    solved, 1 too few matches, 2 non-positive pivot, 3 drained), |ω|, |v|. `handle` is an ofx_rigid_create handle sized
+    for at least P points; `state` is its ordering token (its scratch is hidden state)."""
+    P = points.shape[0]
+    dev = points.device
+    _, H, W = point_image.shape
+    if pose.dtype != torch.float64 or pose.numel() != 12 or not pose.is_contiguous():
+        raise ValueError("rigid_icp: pose must be a contiguous float64 tensor of 12 elements ([R|t], row-major)")
+    cam = _camera(intr, H, W)
+    prm = _lib.RigidParams(float(dist_max), float(cos_min), float(edge_max), int(iters), int(min_matches),
+                           float(damping), float(stop_twist))
+    v = None if valid is None else valid.to(torch.uint8)
+    code = torch.zeros(P, dtype=torch.uint8, device=dev)
+    systems = torch.empty((int(iters), 32), dtype=torch.float64, device=dev)
+    call("ofx_rigid_icp", _lib.c_void_p(handle), ptr(points), ptr(normals), ptr(anchors), ptr(weights), ptr(v), P,
+         ptr(packed_nodes), packed_nodes.shape[0], byref(cam), ptr(point_image), H, W, byref(prm), ptr(pose), ptr(code),
+         ptr(systems), _stream(points))
+    return code, systems
+
+
+@rigid_icp.register_fake
+def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, point_image, intr, dist_max, cos_min,
+      edge_max, iters, min_matches, damping, stop_twist, pose):
+    return (points.new_empty((points.shape[0],), dtype=torch.uint8),
+            points.new_empty((int(iters), 32), dtype=torch.float64))
+
+
 # --------------------------------------------------------------------------------------------- surface points
 @_op("surface_points", mutates_args=("state", "points", "normals", "anchors_out", "weights_out", "voxel", "valid", "code",
                                      "count"))
@@ -461,4 +497,5 @@ def _(state, handle, n_nodes, num_iter):
 
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
-       "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points")
+       "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
+       "rigid_icp")

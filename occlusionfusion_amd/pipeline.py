@@ -156,7 +156,16 @@ class FusionPipeline:
         self.model_counts.append(m["count"].clone())
         return m
 
-    def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, assoc):
+    def _rigid_aligner(self, rigid_iters, n_points):
+        """The pipeline's RigidAligner, (re)made for n_points points; None while no rigid stage is asked for."""
+        from .association import RigidAligner
+        if int(rigid_iters) <= 0:
+            return None
+        if getattr(self, "_rigid", None) is None or self._rigid.max_points < n_points:
+            self._rigid = RigidAligner(n_points, self.device)
+        return self._rigid
+
+    def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc):
         from .association import ProjectiveAssociator, icp_track
         M = int(max_model_points)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
@@ -173,7 +182,7 @@ class FusionPipeline:
         out, log, _ = icp_track(self._vassoc, self.solver, self.nodes_t, self.edges_t, self.ew_t, m["points"],
                                 m["normals"], m["anchors"], m["weights"], m["valid"], fi.im[-1], self.intr,
                                 self.prev_rot, self.prev_trans, (fi.tpos, fi.conf) if motion else None, icp_iters,
-                                **assoc)
+                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M), **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out
@@ -190,7 +199,7 @@ class FusionPipeline:
         return out
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
-                   max_model_points=65536, w_min=1.0, **assoc):
+                   max_model_points=65536, w_min=1.0, rigid_iters=0, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -205,9 +214,14 @@ class FusionPipeline:
         alone then drives the loop. The padded arrays and their valid mask go to the association as they are (no host
         read for the model; model_counts holds each sampling's device [accepted, emitted]). The re-sampling follows the
         integrate in its stream order and the next association waits for it: with overlap=True the pending integrate is
-        enqueued at once (flush()), so the integrate / solve overlap does not apply in this mode."""
+        enqueued at once (flush()), so the integrate / solve overlap does not apply in this mode.
+
+        rigid_iters > 0 (both models): that many rigid point-to-plane iterations of all model points
+        (association.RigidAligner) run before the first association; their pose is folded into the node transforms, so
+        the solve and the integrate see only node transforms. The result then carries "rigid": {"pose", "systems"}."""
         if model == "volume":
-            return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, assoc)
+            return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
+                                      assoc)
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
@@ -221,7 +235,7 @@ class FusionPipeline:
         out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
                                 (fi.tpos, fi.conf) if motion else None, icp_iters,
-                                **assoc)
+                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]), **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out

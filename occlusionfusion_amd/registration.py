@@ -502,7 +502,8 @@ class Registration:
                "source_frame_id": optical_flow_data["source_id"], "target_frame_id": optical_flow_data["target_id"]}
         return res
 
-    def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3, **assoc):
+    def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
+              rigid_iters=0, **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -514,8 +515,11 @@ class Registration:
         rows vanish (nodes as targets, confidence 0). Raises association.TooFewMatches, with no solve launched, if an
         association emits fewer than 4·K = 16 matches. Returns optimize's result dict (frame ids: None and the
         target's "id") plus "assoc": per ICP iteration the accepted count, the emitted count and the histogram of the
-        codes. One host synchronisation per association (its counts) besides the solves' own."""
-        from .association import ProjectiveAssociator, icp_track
+        codes. One host synchronisation per association (its counts) besides the solves' own.
+        rigid_iters > 0: that many rigid point-to-plane iterations of all of source_pcd (association.RigidAligner,
+        ofx_rigid_icp) run first and their pose is folded into the estimate the loop starts from; the result then has
+        "rigid": {"pose" (3,4) f64, "systems"} as device tensors. The stage adds no host synchronisation."""
+        from .association import ProjectiveAssociator, RigidAligner, icp_track
         depth = torch.as_tensor(np.ascontiguousarray(target_frame_data["im"][-1], np.float32), device=self.device)
         self.tgt_pcd, self.pix_2_pcd = depth_2_pc_device(depth, self.intrinsics)
         P = self.source_pcd.shape[0]
@@ -527,19 +531,24 @@ class Registration:
             if nrm.shape[0] != P:
                 nrm = nrm[torch.as_tensor(self.valid_source_verts, device=self.device)]
         assoc.setdefault("max_matches", self.max_matches)
+        if int(rigid_iters) > 0 and (getattr(self, "_rigid", None) is None or self._rigid.max_points < P):
+            self._rigid = RigidAligner(P, self.device)
         out, log, _ = icp_track(self._assoc, self.solver, self.graph.nodes, self.graph.edges, self.graph.edges_weights,
                                 self.source_pcd, nrm, self.point_anchors, self.anchor_weight, None, depth,
                                 self._intr4(), self.prev_rot, self.prev_trans, complete_node_motion_data, icp_iters,
-                                **assoc)
+                                rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None), **assoc)
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)
         self.warpfield.set_node_transforms(R, T)
         warped = self.warpfield.deform_device(self.source_pcd, self.point_anchors, self.anchor_weight)
-        return {"warped_verts": warped, "node_rotations": R.cpu().numpy().astype(np.float64),
-                "node_translations": T.cpu(), "deformed_nodes_to_target": nodes_t + T,
-                "convergence_info": out["convergence_info"], "valid_solve": out["valid_solve"],
-                "source_frame_id": None, "target_frame_id": target_frame_data.get("id"), "assoc": log}
+        res = {"warped_verts": warped, "node_rotations": R.cpu().numpy().astype(np.float64),
+               "node_translations": T.cpu(), "deformed_nodes_to_target": nodes_t + T,
+               "convergence_info": out["convergence_info"], "valid_solve": out["valid_solve"],
+               "source_frame_id": None, "target_frame_id": target_frame_data.get("id"), "assoc": log}
+        if "rigid" in out:
+            res["rigid"] = out["rigid"]
+        return res
 
 
 def run_arap(solver, reduced_graph_dict, model_data, graph, log=None):
