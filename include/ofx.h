@@ -43,6 +43,10 @@
  *   ofx_surface_*           (new) skinned surface points of the TSDF, the tracking model — (no reference twin: the
  *                           reference re-meshes and re-skins per frame, tsdf.get_deformed_model / optimizer.update in
  *                           fusion_tests/lepard_nicp_test.py:471,537. Parity unpinned; restated by tests/surface_ref.py)
+ *   ofx_splat_*             (new) z-buffer of the warped model points in the live frame and the occlusion code of every
+ *                           point — (no reference twin: the reference renders the live model from a warped marching-
+ *                           cubes mesh, tsdf.get_deformed_model and NonRigidICP/model/point_render.py. Parity unpinned;
+ *                           restated op for op by tests/splat_ref.py)
  *   ofx_depth_to_pc         Registration.optimize target cloud: depth_2_pc, NonRigidICP/model/geometry.py:44-59,
  *                           mask compaction, map_pixel_to_pcd              registration_fusion.py:104-109,388-395
  *   ofx_pixel_anchors_euclidean  csrc compute_pixel_anchors_euclidean     csrc/cpu/graph_proc.cpp:610-709
@@ -386,6 +390,49 @@ int ofx_rigid_icp(void* handle, const float* points, const float* normals, const
                   const uint8_t* valid, int64_t n_points, const float* packed_nodes, int32_t n_nodes,
                   const ofx_camera* cam, const float* point_image, int32_t height, int32_t width,
                   const ofx_rigid_params* prm, double* pose, uint8_t* code, double* systems, ofx_stream_t s);
+
+/* ---------------- Model z-buffer and occlusion gate (new capability; the reference has none — parity unpinned) ----------------
+ * The warped model points splatted as oriented discs of world radius rho into a depth and an index image of the live frame,
+ * and the occlusion code of every point against that image: what tells the tracker which model points the model itself
+ * hides, and what shows the fused model where the camera is. Inputs and their checks are ofx_associate's (K = 4; anchors,
+ * weights and packed_nodes 16-byte aligned; normals and valid may be NULL). Restated op for op by tests/splat_ref.py.
+ * Per point (f32, no contraction, every step fixed; the first code that applies):
+ *   x', n' = ofx_associate's warped point and normalised warped normal (the same device code); a point with valid == 0
+ *            keeps its position in `warped` and its normal in `warped_normals`; normals == NULL: n' = (0, 0, -1)
+ *   1  valid[p] == 0, or an anchor outside [0, n_nodes)
+ *   2  x' non-finite, z' <= 0, or its pixel (u, v) — the one ofx_visibility_f32 / ofx_associate take — off the image
+ *   3  back-facing: s = (n'_x*x' + n'_y*y') + n'_z*z', rejected if !(s < 0) (a NaN normal lands here)
+ * A live point (none of the above) writes its disc: r_u = clamp(ceilf((fx*rho)/z'), 0, OFX_SPLAT_RMAX), r_v the same with
+ * fy (divisions correctly rounded); for every pixel (uu, vv) = (u + du, v + dv), |du| <= r_u, |dv| <= r_v, inside the image:
+ *   centre (du = dv = 0): z_p = z', always written — the buffer at a live point's own pixel is never behind the point
+ *   others: dx = (f32(uu) - cx)/fx, dy = (f32(vv) - cy)/fy, den = (n'_x*dx + n'_y*dy) + n'_z, z_p = s/den (divisions
+ *           correctly rounded: the ray's hit on the point's tangent plane), e = (dx*z_p - x', dy*z_p - y', z_p - z'),
+ *           d2 = (e_x^2 + e_y^2) + e_z^2; written only if den < 0 && z_p > 0 && z_p finite && d2 <= rho*rho (a true disc of
+ *           radius rho: an ellipse on the image, thin at grazing angles)
+ *   the write is a 64-bit unsigned atomic minimum of key = (u64)float_bits(z_p) << 32 | (u32)p on zbuf[vv*W + uu]: z_p is
+ *   positive and finite, so its bits order as the float does; exact ties in z go to the lower point index; a minimum does not
+ *   depend on arrival order, so two calls and two handles give the same bytes.
+ * After all points: depth[pix] = the float of the key's high word (0 where nothing was written), index[pix] = its low word
+ * (-1 where nothing was written), and for a live point
+ *   4  occluded: (z' - depth[v*W + u]) > occl_margin
+ *   0  visible
+ * Outputs (each may be NULL): depth f32[H*W], index i32[H*W], code u8[P], warped f32[P,3], warped_normals f32[P,3] (given
+ * without normals: OFX_ERR_ARG). H = cam->height, W = cam->width. splat_radius must be finite and >= 0, occl_margin not NaN.
+ * Stream-ordered: three launches, no allocation and no host sync inside; the handle owns the u64 z-buffer of max_pixels
+ * words and 8 bytes per point of scratch (n_points above max_points, or width*height above max_pixels, is OFX_ERR_ARG).
+ * n_points = 0 is legal: depth all 0, index all -1. */
+typedef struct ofx_splat_params {
+  float   splat_radius;   /* rho, metres: world radius of a point's disc */
+  float   occl_margin;    /* metres of z */
+  int32_t _pad[2];
+} ofx_splat_params;
+#define OFX_SPLAT_RMAX 4
+int ofx_splat_create(int64_t max_points, int64_t max_pixels, void** handle);
+int ofx_splat_destroy(void* handle);
+int ofx_splat_points(void* handle, const float* points, const float* normals, const int32_t* anchors, const float* weights,
+                     const uint8_t* valid, int64_t n_points, const float* packed_nodes, int32_t n_nodes,
+                     const ofx_camera* cam, const ofx_splat_params* prm, float* depth, int32_t* index, uint8_t* code,
+                     float* warped, float* warped_normals, ofx_stream_t s);
 
 /* ---------------- Skinned surface points of the TSDF (new capability; the reference has none — parity unpinned) ----------------
  * The tracking model read off the volume itself: canonical surface points, their outward normals and their anchors and

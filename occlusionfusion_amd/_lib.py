@@ -36,6 +36,13 @@ class RigidParams(ctypes.Structure):
                 ("min_matches", c_int32), ("damping", c_double), ("stop_twist", c_double)]
 
 
+class SplatParams(ctypes.Structure):
+    _fields_ = [("splat_radius", c_float), ("occl_margin", c_float), ("_pad", c_int32 * 2)]
+
+
+SPLAT_RMAX = 4   # OFX_SPLAT_RMAX (include/ofx.h)
+
+
 class GnParams(ctypes.Structure):
     _fields_ = [("num_iter", c_int32), ("use_edge_weighting", c_int32), ("pcg_max_iter", c_int32), ("pcg_warm", c_int32),
                 ("lambda_flow", c_double), ("lambda_depth", c_double), ("lambda_arap", c_double),
@@ -99,6 +106,9 @@ _SIGS = {
     "ofx_rigid_create": [c_int64, P],
     "ofx_rigid_destroy": [P],
     "ofx_rigid_icp": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P],
+    "ofx_splat_create": [c_int64, c_int64, P],
+    "ofx_splat_destroy": [P],
+    "ofx_splat_points": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, P, P, P, P, P, P],
     "ofx_surface_create": [c_int32, P],
     "ofx_surface_destroy": [P],
     "ofx_surface_points": [P, P, P, P, P, c_int32, P, P, c_int32, c_float, c_int32, P, P, P, P, P, P, P, P, P],

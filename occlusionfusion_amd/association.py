@@ -8,7 +8,9 @@ kernel + an ordered compaction). It has no reference twin; its geometric relativ
 (NonRigidICP/model/loss.py:275-292). icp_track is the loop around it that Registration.track and
 FusionPipeline.track_step share; RigidAligner (torch.ops.ofx.rigid_icp -> ofx_rigid_icp) is its optional first stage, a
 rigid point-to-plane ICP of all model points whose pose fold_rigid folds into the node transforms. This is the data term for what the camera sees: motion of occluded nodes still needs the
-motion-completion input.
+motion-completion input. ModelRenderer (torch.ops.ofx.splat_points -> ofx_splat_points) is the model's own z-buffer in the
+live frame: with occlusion=True, icp_track keeps the points that the model itself hides out of both stages, and
+WarpField.render_live shows the fused model where the camera is.
 """
 import numpy as np
 import torch
@@ -175,6 +177,81 @@ class RigidAligner:
         return out
 
 
+class ModelRenderer:
+    """Owns an ofx_splat handle (a u64 z-buffer of max_pixels words and per-point scratch for up to max_points points):
+    the live-frame z-buffer of the warped model points (torch.ops.ofx.splat_points -> ofx_splat_points) — the depth,
+    index and normal image of the model where the camera is, and for every point whether the model itself hides it."""
+
+    def __init__(self, max_points, max_pixels, device=None):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.max_points, self.max_pixels = int(max_points), int(max_pixels)
+        self._h = _lib.c_void_p()
+        with torch.cuda.device(self.device):
+            call("ofx_splat_create", self.max_points, self.max_pixels, byref(self._h))
+        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)   # ofx::splat_points ordering token
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.lib.ofx_splat_destroy(h)
+            except Exception:
+                pass
+        self._h = None
+
+    def render(self, points, normals, anchors, weights, valid, warpfield_or_packed_nodes, intr, height, width,
+               splat_radius, occl_margin=0.01, normal_map=False):
+        """Splat the points (inputs as ProjectiveAssociator.associate) under the transforms of a WarpField or of a
+        packed (N,16) node tensor into a height x width image: every point a disc of world radius splat_radius (metres)
+        on its tangent plane (facing the camera without normals), the nearest disc per pixel. Returns a dict of device
+        tensors: depth f32 (H,W) (0 = nothing), index i32 (H,W) (-1 = nothing), code u8 (P,) (SPLAT_CODE_NAMES; 4 =
+        occluded: more than occl_margin metres behind the buffer at the point's own pixel), warped (P,3), visible u8
+        (P,) (code == 0) and, with normal_map=True (normals required), normals f32 (3,H,W): the warped normal of the
+        point that owns each pixel, zeros where none does. Everything is enqueued on torch's current stream; nothing is
+        read back."""
+        d = self.device
+        pts = _f32(points, d, (-1, 3))
+        P = pts.shape[0]
+        H, W = int(height), int(width)
+        if P > self.max_points:
+            raise ValueError(f"{P} points exceed the renderer's capacity ({self.max_points})")
+        if H * W > self.max_pixels:
+            raise ValueError(f"{H} x {W} pixels exceed the renderer's capacity ({self.max_pixels})")
+        if normal_map and normals is None:
+            raise ValueError("normal_map=True needs the points' normals")
+        packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
+                  else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
+        a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
+        a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
+        v = None
+        if valid is not None:
+            v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
+            v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
+        depth, index, code, warped, wn = torch.ops.ofx.splat_points(
+            self._state, self._h.value, pts, _f32(normals, d, (P, 3)), a, _f32(weights, d, (P, 4)), v, packed,
+            [float(x) for x in intr[:4]], H, W, float(splat_radius), float(occl_margin))
+        out = {"depth": depth, "index": index, "code": code, "warped": warped, "visible": (code == 0).to(torch.uint8)}
+        if normal_map:
+            hit = index >= 0
+            if P:
+                nm = wn[index.clamp(min=0).reshape(-1).long()].reshape(H, W, 3)
+                nm = torch.where(hit[..., None], nm, torch.zeros((), dtype=torch.float32, device=d))
+            else:
+                nm = torch.zeros((H, W, 3), dtype=torch.float32, device=d)
+            out["normals"] = nm.permute(2, 0, 1).contiguous()
+        return out
+
+
+SPLAT_CODE_NAMES = ("visible", "invalid_skin", "off_image", "back_facing", "occluded")
+
+
+def default_splat_radius(voxel_size, with_normals):
+    """The disc radius the tracking layers use for a model sampled from a volume: the voxel size when the model carries
+    normals (tilted discs tile the surface without covering what lies behind its silhouette), half of it without
+    (fronto-parallel discs of a full voxel hide too much of a slanted surface)."""
+    return float(voxel_size) if with_normals else 0.5 * float(voxel_size)
+
+
 def fold_rigid(nodes, rot, trans, pose):
     """Fold a rigid pose [R|t] (3,4) into the node transforms: R_k' = R·R_k, T_k' = R·(g_k + T_k) + t − g_k, computed in
     f64 on the pose's device and rounded once to f32; rot / trans None = the identity. The ED warp of any point then
@@ -206,7 +283,7 @@ def fold_rigid(nodes, rot, trans, pose):
 
 def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
               valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3,
-              rigid_iters=0, rigid=None, **assoc):
+              rigid_iters=0, rigid=None, occlusion=False, renderer=None, splat_radius=None, occl_margin=0.01, **assoc):
     """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
     associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
     matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
@@ -217,7 +294,15 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     of all the points (rigid: a RigidAligner, required then) from the identity pose around the current estimate, with
     the association's gates; the pose is folded into the estimate (fold_rigid) and the loop goes on from there. The
     stage reads nothing back: a failed rigid stage folds an unchanged pose. The result then gains "rigid": dict(pose,
-    systems), device tensors."""
+    systems), device tensors.
+
+    occlusion=True puts the model's own z-buffer in front of every stage (renderer: a ModelRenderer, and splat_radius,
+    both required then): before the rigid stage and before every association the model is rendered under the current
+    estimate (ModelRenderer.render with splat_radius / occl_margin) and valid & visible takes the place of valid for
+    that stage, so a point that another part of the model hides is not matched to the surface in front of it. The mask
+    stays on the device (no added host synchronisation), and the iteration's packed node tensor is built once for the
+    render and the association. The result then gains "render": the last render's dict. occlusion=False is the loop
+    as it was."""
     from .image_proc import backproject_depth_device
     rigid_iters = int(rigid_iters)
     if rigid_iters < 0:
@@ -226,6 +311,8 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         raise ValueError("icp_iters must be at least 1")
     if rigid_iters > 0 and rigid is None:
         raise ValueError("rigid_iters > 0 needs a RigidAligner (rigid=...)")
+    if occlusion and (renderer is None or splat_radius is None):
+        raise ValueError("occlusion=True needs a ModelRenderer (renderer=...) and a splat_radius")
     d = solver.device
     prm = dict(ASSOC_DEFAULTS)
     unknown = set(assoc) - set(prm)
@@ -240,15 +327,34 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     tloc, tconf = complete_node_motion_data if complete_node_motion_data is not None else (None, None)
     rot, trans, out, log = prev_rot, prev_trans, None, []
     rig = None
+    ren = None
+    H, W = int(vm.shape[1]), int(vm.shape[2])
+
+    def seen(packed):
+        """valid & visible under the packed transforms (device u8), and the render it came from"""
+        r = renderer.render(points, normals, anchors, weights, valid, packed, (fx, fy, cx, cy), H, W, splat_radius,
+                            occl_margin)
+        if valid is None:
+            return r["visible"], r
+        v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
+        return (v.to(device=d).reshape(-1) != 0).to(torch.uint8) & r["visible"], r
+
     if rigid_iters > 0:
         gates = {k: prm[k] for k in ("dist_max", "cos_min", "edge_max")}
-        r = rigid.align(points, normals, anchors, weights, valid, pack_transforms(graph_nodes, rot, trans, d), vm,
+        packed = pack_transforms(graph_nodes, rot, trans, d)
+        v_stage = valid
+        if occlusion:
+            v_stage, ren = seen(packed)
+        r = rigid.align(points, normals, anchors, weights, v_stage, packed, vm,
                         (fx, fy, cx, cy), pose=None, iters=rigid_iters, **gates)
         rot, trans = fold_rigid(graph_nodes, rot, trans, r["pose"])
         rig = {"pose": r["pose"], "systems": r["systems"]}
     for it in range(int(icp_iters)):
-        m = associator.associate(points, normals, anchors, weights, valid, pack_transforms(graph_nodes, rot, trans, d),
-                                 vm, (fx, fy, cx, cy), **prm)
+        packed = pack_transforms(graph_nodes, rot, trans, d)
+        v_stage = valid
+        if occlusion:
+            v_stage, ren = seen(packed)
+        m = associator.associate(points, normals, anchors, weights, v_stage, packed, vm, (fx, fy, cx, cy), **prm)
         log.append({"accepted": m["accepted"], "emitted": m["emitted"], "histogram": m["histogram"]})
         if m["emitted"] < 16:
             raise TooFewMatches(f"projective association {it} emitted {m['emitted']} matches of {m['accepted']} accepted "
@@ -258,4 +364,6 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         rot, trans = out["node_rotations"], out["node_translations"]
     if rig is not None:
         out["rigid"] = rig
+    if ren is not None:
+        out["render"] = ren
     return out, log, vm

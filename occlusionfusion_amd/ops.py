@@ -270,6 +270,44 @@ def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, poi
             points.new_empty((int(iters), 32), dtype=torch.float64))
 
 
+# --------------------------------------------------------------------------------------------- model z-buffer
+@_op("splat_points", mutates_args=("state",))
+def splat_points(state: Tensor, handle: int, points: Tensor, normals: Optional[Tensor], anchors: Tensor, weights: Tensor,
+                 valid: Optional[Tensor], packed_nodes: Tensor, intr: List[float], height: int, width: int,
+                 splat_radius: float, occl_margin: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """ofx_splat_points (new capability, no reference twin): the z-buffer of the points (P,3) — skinned and warped as in
+    `associate`, each a disc of world radius splat_radius facing along its warped normal — in a height x width image
+    under intr -> depth f32 (H,W) (0 = nothing), index i32 (H,W) (the point that owns the pixel, -1 = nothing), code u8
+    (P,) (0 visible, 1 invalid skin, 2 off the image / behind / non-finite, 3 back-facing, 4 occluded: more than
+    occl_margin behind the buffer at its own pixel), warped (P,3), warped_normals (P,3) ((0,3) without normals).
+    `handle` is an ofx_splat_create handle sized for at least P points and height·width pixels; `state` is its ordering
+    token (its z-buffer is hidden state)."""
+    P = points.shape[0]
+    dev = points.device
+    H, W = int(height), int(width)
+    cam = _camera(intr, H, W)
+    prm = _lib.SplatParams(float(splat_radius), float(occl_margin))
+    v = None if valid is None else valid.to(torch.uint8)
+    depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    index = torch.empty((H, W), dtype=torch.int32, device=dev)
+    code = torch.empty(P, dtype=torch.uint8, device=dev)
+    warped = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    wn = torch.empty((P if normals is not None else 0, 3), dtype=torch.float32, device=dev)
+    call("ofx_splat_points", _lib.c_void_p(handle), ptr(points), ptr(normals), ptr(anchors), ptr(weights), ptr(v), P,
+         ptr(packed_nodes), packed_nodes.shape[0], byref(cam), byref(prm), ptr(depth), ptr(index), ptr(code),
+         ptr(warped), ptr(wn) if normals is not None else None, _stream(points))
+    return depth, index, code, warped, wn
+
+
+@splat_points.register_fake
+def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, intr, height, width, splat_radius,
+      occl_margin):
+    P, f = points.shape[0], torch.float32
+    return (points.new_empty((height, width), dtype=f), points.new_empty((height, width), dtype=torch.int32),
+            points.new_empty((P,), dtype=torch.uint8), points.new_empty((P, 3), dtype=f),
+            points.new_empty((P if normals is not None else 0, 3), dtype=f))
+
+
 # --------------------------------------------------------------------------------------------- surface points
 @_op("surface_points", mutates_args=("state", "points", "normals", "anchors_out", "weights_out", "voxel", "valid", "code",
                                      "count"))
@@ -498,4 +536,4 @@ def _(state, handle, n_nodes, num_iter):
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
-       "rigid_icp")
+       "rigid_icp", "splat_points")

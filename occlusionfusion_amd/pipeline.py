@@ -165,7 +165,23 @@ class FusionPipeline:
             self._rigid = RigidAligner(n_points, self.device)
         return self._rigid
 
-    def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc):
+    def _occlusion(self, occlusion, splat_radius, occl_margin, n_points, depth, with_normals):
+        """icp_track's occlusion keywords: the pipeline's ModelRenderer, (re)made for n_points points and the depth
+        image's pixels, and the default splat radius (the voxel size with normals, half of it without); {} while no
+        occlusion gate is asked for."""
+        from .association import ModelRenderer, default_splat_radius
+        if not occlusion:
+            return {}
+        n_pix = int(depth.shape[0]) * int(depth.shape[1])
+        ren = getattr(self, "_renderer", None)
+        if ren is None or ren.max_points < n_points or ren.max_pixels < n_pix:
+            self._renderer = ModelRenderer(n_points, n_pix, self.device)
+        if splat_radius is None:
+            splat_radius = default_splat_radius(self.vol._voxel_size, with_normals)
+        return dict(occlusion=True, renderer=self._renderer, splat_radius=splat_radius, occl_margin=occl_margin)
+
+    def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
+                      occ=(False, None, 0.01)):
         from .association import ProjectiveAssociator, icp_track
         M = int(max_model_points)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
@@ -182,7 +198,8 @@ class FusionPipeline:
         out, log, _ = icp_track(self._vassoc, self.solver, self.nodes_t, self.edges_t, self.ew_t, m["points"],
                                 m["normals"], m["anchors"], m["weights"], m["valid"], fi.im[-1], self.intr,
                                 self.prev_rot, self.prev_trans, (fi.tpos, fi.conf) if motion else None, icp_iters,
-                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M), **assoc)
+                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M),
+                                **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out
@@ -199,7 +216,8 @@ class FusionPipeline:
         return out
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
-                   max_model_points=65536, w_min=1.0, rigid_iters=0, **assoc):
+                   max_model_points=65536, w_min=1.0, rigid_iters=0, occlusion=False, splat_radius=None,
+                   occl_margin=0.01, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -218,10 +236,16 @@ class FusionPipeline:
 
         rigid_iters > 0 (both models): that many rigid point-to-plane iterations of all model points
         (association.RigidAligner) run before the first association; their pose is folded into the node transforms, so
-        the solve and the integrate see only node transforms. The result then carries "rigid": {"pose", "systems"}."""
+        the solve and the integrate see only node transforms. The result then carries "rigid": {"pose", "systems"}.
+
+        occlusion=True (both models): the model's own z-buffer goes in front of the rigid stage and of every association
+        (association.ModelRenderer, owned by the pipeline): points that the model itself hides under the current
+        estimate, by more than occl_margin metres, are left out of that stage. splat_radius defaults to the volume's
+        voxel size for the volume model (it carries normals) and to half of it for the canonical points (they do not).
+        The result then carries "render": the last render's dict of device tensors. No host read is added."""
         if model == "volume":
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
-                                      assoc)
+                                      assoc, (occlusion, splat_radius, occl_margin))
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
@@ -235,7 +259,9 @@ class FusionPipeline:
         out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
                                 (fi.tpos, fi.conf) if motion else None, icp_iters,
-                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]), **assoc)
+                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
+                                **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),
+                                **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out

@@ -503,7 +503,7 @@ class Registration:
         return res
 
     def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
-              rigid_iters=0, **assoc):
+              rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -518,8 +518,13 @@ class Registration:
         codes. One host synchronisation per association (its counts) besides the solves' own.
         rigid_iters > 0: that many rigid point-to-plane iterations of all of source_pcd (association.RigidAligner,
         ofx_rigid_icp) run first and their pose is folded into the estimate the loop starts from; the result then has
-        "rigid": {"pose" (3,4) f64, "systems"} as device tensors. The stage adds no host synchronisation."""
-        from .association import ProjectiveAssociator, RigidAligner, icp_track
+        "rigid": {"pose" (3,4) f64, "systems"} as device tensors. The stage adds no host synchronisation.
+        occlusion=True: before the rigid stage and every association the model is rendered under the current estimate
+        (association.ModelRenderer, ofx_splat_points, owned by this object) and the points the model itself hides —
+        more than occl_margin metres behind its z-buffer — are left out of that stage; splat_radius (metres) defaults
+        to the volume's voxel size when the model carries normals and to half of it when it does not. The result then
+        has "render": the last render's dict of device tensors. No host synchronisation is added."""
+        from .association import ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track
         depth = torch.as_tensor(np.ascontiguousarray(target_frame_data["im"][-1], np.float32), device=self.device)
         self.tgt_pcd, self.pix_2_pcd = depth_2_pc_device(depth, self.intrinsics)
         P = self.source_pcd.shape[0]
@@ -533,10 +538,22 @@ class Registration:
         assoc.setdefault("max_matches", self.max_matches)
         if int(rigid_iters) > 0 and (getattr(self, "_rigid", None) is None or self._rigid.max_points < P):
             self._rigid = RigidAligner(P, self.device)
+        occ = {}
+        if occlusion:
+            if splat_radius is None:
+                vol = getattr(self.warpfield, "tsdf", None)
+                if vol is None:
+                    raise ValueError("occlusion=True needs a splat_radius: the warp field has no volume to take it from")
+                splat_radius = default_splat_radius(vol._voxel_size, nrm is not None)
+            n_pix = int(depth.shape[0]) * int(depth.shape[1])
+            ren = getattr(self, "_renderer", None)
+            if ren is None or ren.max_points < P or ren.max_pixels < n_pix:
+                self._renderer = ModelRenderer(P, n_pix, self.device)
+            occ = dict(occlusion=True, renderer=self._renderer, splat_radius=splat_radius, occl_margin=occl_margin)
         out, log, _ = icp_track(self._assoc, self.solver, self.graph.nodes, self.graph.edges, self.graph.edges_weights,
                                 self.source_pcd, nrm, self.point_anchors, self.anchor_weight, None, depth,
                                 self._intr4(), self.prev_rot, self.prev_trans, complete_node_motion_data, icp_iters,
-                                rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None), **assoc)
+                                rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None), **occ, **assoc)
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)
@@ -548,6 +565,8 @@ class Registration:
                "source_frame_id": None, "target_frame_id": target_frame_data.get("id"), "assoc": log}
         if "rigid" in out:
             res["rigid"] = out["rigid"]
+        if "render" in out:
+            res["render"] = out["render"]
         return res
 
 

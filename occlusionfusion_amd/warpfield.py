@@ -486,6 +486,34 @@ class WarpField:
             res["histogram"] = [int(x) for x in host[2:2 + len(CODE_NAMES)]]
         return res
 
+    def render_live(self, max_points=65536, w_min=1.0, splat_radius=None, intr=None, height=None, width=None):
+        """The fused model seen from the camera in the live frame: surface_points(sync=False) splatted under the warp
+        field's current transforms (association.ModelRenderer, ofx_splat_points; no reference twin — the reference
+        warps a marching-cubes mesh and hands it to an external renderer). -> dict of device tensors: depth f32 (H,W)
+        (0 = nothing), normals f32 (3,H,W), index i32 (H,W) (row of the sampled model, -1 = nothing), and the per-point
+        code / visible / warped of ModelRenderer.render, plus "model": the sampled arrays (surface_points' dict; its
+        voxel column ties a pixel to its voxel). splat_radius defaults to the voxel size; intr (fx, fy, cx, cy), height
+        and width default to the volume's camera and its last frame's size. No mesh and no host read."""
+        from .association import ModelRenderer, default_splat_radius
+        t = self.tsdf
+        if intr is None:
+            K = t.cam_intr
+            intr = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
+        if height is None or width is None:
+            if getattr(t, "depth_t", None) is None:
+                raise ValueError("render_live needs height and width: the volume has seen no frame to take them from")
+            height, width = int(t.depth_t.shape[0]), int(t.depth_t.shape[1])
+        if splat_radius is None:
+            splat_radius = default_splat_radius(t._voxel_size, True)
+        m = self.surface_points(int(max_points), w_min, sync=False)
+        ren = getattr(self, "_renderer", None)
+        if ren is None or ren.max_points < int(max_points) or ren.max_pixels < int(height) * int(width):
+            ren = self._renderer = ModelRenderer(int(max_points), int(height) * int(width), self.device)
+        out = ren.render(m["points"], m["normals"], m["anchors"], m["weights"], m["valid"], self, intr, height, width,
+                         splat_radius, normal_map=True)
+        out["model"] = m
+        return out
+
     # ------------------------------------------------------------------ deformation
     def deform_device(self, points, anchors, weights, valid=None, normals=False):
         pts = _t(points, self.device, torch.float32).reshape(-1, 3)
