@@ -48,26 +48,56 @@ def pack_transforms(nodes, rot, trans, device):
     return out
 
 
-class ProjectiveAssociator:
-    """Owns an ofx_assoc handle (rank and tile scratch for up to max_points points) and the last call's outputs."""
+def _skinned(points, normals, anchors, weights, valid, warpfield_or_packed_nodes, device, capacity, what):
+    """The skinned inputs every entry point takes, as the operators want them -> (pts (P,3), nrm (P,3) or None, anchors
+    i32 (P,4), weights (P,4), valid u8 (P,) or None, packed (N,16), P). `what` names the owner of `capacity`."""
+    d = device
+    pts = _f32(points, d, (-1, 3))
+    P = pts.shape[0]
+    if P > capacity:
+        raise ValueError(f"{P} points exceed the {what}'s capacity ({capacity})")
+    packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
+              else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
+    a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
+    a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
+    v = None
+    if valid is not None:
+        v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
+        v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
+    return pts, _f32(normals, d, (P, 3)), a, _f32(weights, d, (P, 4)), v, packed, P
 
-    def __init__(self, max_points, device=None):
+
+class _Handle:
+    """A device, a C handle made by `create`(*args, &handle) on it and freed by `destroy`, and the operator's ordering
+    token."""
+    _create = _destroy = None
+
+    def _open(self, device, *args):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.max_points = int(max_points)
         self._h = _lib.c_void_p()
         with torch.cuda.device(self.device):
-            call("ofx_assoc_create", self.max_points, byref(self._h))
-        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)   # ofx::associate ordering token
-        self.last = None
+            call(self._create, *args, byref(self._h))
+        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             try:
-                _lib.lib.ofx_assoc_destroy(h)
+                getattr(_lib.lib, self._destroy)(h)
             except Exception:
                 pass
         self._h = None
+
+
+class ProjectiveAssociator(_Handle):
+    """Owns an ofx_assoc handle (rank and tile scratch for up to max_points points) and the last call's outputs."""
+
+    _create, _destroy = "ofx_assoc_create", "ofx_assoc_destroy"
+
+    def __init__(self, max_points, device=None):
+        self.max_points = int(max_points)
+        self._open(device, self.max_points)
+        self.last = None
 
     def associate(self, points, normals, anchors, weights, valid, warpfield_or_packed_nodes, point_image, intr,
                   dist_max=0.05, cos_min=0.5, edge_max=0.03, mode="plane", max_matches=10000):
@@ -84,23 +114,13 @@ class ProjectiveAssociator:
         Reading the counts is the tracking loop's one host synchronisation per association; everything else is
         enqueued on torch's current stream."""
         d = self.device
-        pts = _f32(points, d, (-1, 3))
-        P = pts.shape[0]
-        if P > self.max_points:
-            raise ValueError(f"{P} points exceed the associator's capacity ({self.max_points})")
-        packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
-                  else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
-        a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
-        a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
-        v = None
-        if valid is not None:
-            v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
-            v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
+        pts, nrm, a, w, v, packed, P = _skinned(points, normals, anchors, weights, valid, warpfield_or_packed_nodes, d,
+                                                self.max_points, "associator")
         vm = _f32(point_image, d)
         assert vm.dim() == 3 and vm.shape[0] == 3, "point image must be (3, H, W)"
-        out = torch.ops.ofx.associate(self._state, self._h.value, pts, _f32(normals, d, (P, 3)), a,
-                                      _f32(weights, d, (P, 4)), v, packed, vm, [float(x) for x in intr[:4]],
-                                      float(dist_max), float(cos_min), float(edge_max), MODES[mode], int(max_matches))
+        out = torch.ops.ofx.associate(self._state, self._h.value, pts, nrm, a, w, v, packed, vm,
+                                      [float(x) for x in intr[:4]], float(dist_max), float(cos_min), float(edge_max),
+                                      MODES[mode], int(max_matches))
         code, tgt_all, warped, midx, src, tgt, a_o, w_o, count = out
         hist = torch.bincount(code.to(torch.int64), minlength=len(CODE_NAMES))
         host = torch.cat([count.to(torch.int64), hist]).cpu().tolist()   # the one host sync
@@ -111,26 +131,15 @@ class ProjectiveAssociator:
         return self.last
 
 
-class RigidAligner:
+class RigidAligner(_Handle):
     """Owns an ofx_rigid handle (the workgroup records of the reduction for up to max_points points): the rigid,
     6-unknown point-to-plane ICP in front of the non-rigid solve (torch.ops.ofx.rigid_icp -> ofx_rigid_icp)."""
 
-    def __init__(self, max_points, device=None):
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.max_points = int(max_points)
-        self._h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            call("ofx_rigid_create", self.max_points, byref(self._h))
-        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)   # ofx::rigid_icp ordering token
+    _create, _destroy = "ofx_rigid_create", "ofx_rigid_destroy"
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib.ofx_rigid_destroy(h)
-            except Exception:
-                pass
-        self._h = None
+    def __init__(self, max_points, device=None):
+        self.max_points = int(max_points)
+        self._open(device, self.max_points)
 
     def align(self, points, normals, anchors, weights, valid, warpfield_or_packed_nodes, point_image, intr, pose=None,
               iters=4, dist_max=0.05, cos_min=0.5, edge_max=0.03, damping=1e-6, min_matches=6, stop_twist=0.0,
@@ -142,18 +151,8 @@ class RigidAligner:
         sync=True: then pose_host / systems_host (numpy) and the per-iteration lists accepted / rms (sqrt(Σr²/count),
         nan without matches) / status are added, at the cost of one host synchronisation."""
         d = self.device
-        pts = _f32(points, d, (-1, 3))
-        P = pts.shape[0]
-        if P > self.max_points:
-            raise ValueError(f"{P} points exceed the aligner's capacity ({self.max_points})")
-        packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
-                  else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
-        a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
-        a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
-        v = None
-        if valid is not None:
-            v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
-            v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
+        pts, nrm, a, w, v, packed, P = _skinned(points, normals, anchors, weights, valid, warpfield_or_packed_nodes, d,
+                                                self.max_points, "aligner")
         vm = _f32(point_image, d)
         assert vm.dim() == 3 and vm.shape[0] == 3, "point image must be (3, H, W)"
         if pose is None:
@@ -161,10 +160,10 @@ class RigidAligner:
         else:
             p = pose if isinstance(pose, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(pose, np.float64))
             p = p.to(device=d, dtype=torch.float64).reshape(3, 4).clone().contiguous()
-        code, systems = torch.ops.ofx.rigid_icp(self._state, self._h.value, pts, _f32(normals, d, (P, 3)), a,
-                                                _f32(weights, d, (P, 4)), v, packed, vm, [float(x) for x in intr[:4]],
-                                                float(dist_max), float(cos_min), float(edge_max), int(iters),
-                                                int(min_matches), float(damping), float(stop_twist), p)
+        code, systems = torch.ops.ofx.rigid_icp(self._state, self._h.value, pts, nrm, a, w, v, packed, vm,
+                                                [float(x) for x in intr[:4]], float(dist_max), float(cos_min),
+                                                float(edge_max), int(iters), int(min_matches), float(damping),
+                                                float(stop_twist), p)
         out = {"pose": p, "systems": systems, "code": code}
         if sync:
             host = torch.cat([p.reshape(-1), systems.reshape(-1)]).cpu().numpy()   # the one host sync
@@ -177,27 +176,16 @@ class RigidAligner:
         return out
 
 
-class ModelRenderer:
+class ModelRenderer(_Handle):
     """Owns an ofx_splat handle (a u64 z-buffer of max_pixels words and per-point scratch for up to max_points points):
     the live-frame z-buffer of the warped model points (torch.ops.ofx.splat_points -> ofx_splat_points) — the depth,
     index and normal image of the model where the camera is, and for every point whether the model itself hides it."""
 
-    def __init__(self, max_points, max_pixels, device=None):
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.max_points, self.max_pixels = int(max_points), int(max_pixels)
-        self._h = _lib.c_void_p()
-        with torch.cuda.device(self.device):
-            call("ofx_splat_create", self.max_points, self.max_pixels, byref(self._h))
-        self._state = torch.zeros(1, dtype=torch.int32, device=self.device)   # ofx::splat_points ordering token
+    _create, _destroy = "ofx_splat_create", "ofx_splat_destroy"
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib.ofx_splat_destroy(h)
-            except Exception:
-                pass
-        self._h = None
+    def __init__(self, max_points, max_pixels, device=None):
+        self.max_points, self.max_pixels = int(max_points), int(max_pixels)
+        self._open(device, self.max_points, self.max_pixels)
 
     def render(self, points, normals, anchors, weights, valid, warpfield_or_packed_nodes, intr, height, width,
                splat_radius, occl_margin=0.01, normal_map=False):
@@ -210,26 +198,16 @@ class ModelRenderer:
         point that owns each pixel, zeros where none does. Everything is enqueued on torch's current stream; nothing is
         read back."""
         d = self.device
-        pts = _f32(points, d, (-1, 3))
-        P = pts.shape[0]
         H, W = int(height), int(width)
-        if P > self.max_points:
-            raise ValueError(f"{P} points exceed the renderer's capacity ({self.max_points})")
+        pts, nrm, a, w, v, packed, P = _skinned(points, normals, anchors, weights, valid, warpfield_or_packed_nodes, d,
+                                                self.max_points, "renderer")
         if H * W > self.max_pixels:
             raise ValueError(f"{H} x {W} pixels exceed the renderer's capacity ({self.max_pixels})")
         if normal_map and normals is None:
             raise ValueError("normal_map=True needs the points' normals")
-        packed = (warpfield_or_packed_nodes.packed_nodes() if hasattr(warpfield_or_packed_nodes, "packed_nodes")
-                  else _f32(warpfield_or_packed_nodes, d, (-1, 16)))
-        a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(anchors))
-        a = a.to(device=d, dtype=torch.int32).contiguous().reshape(P, 4)
-        v = None
-        if valid is not None:
-            v = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(valid))
-            v = v.to(device=d).to(torch.uint8).contiguous().reshape(P)
         depth, index, code, warped, wn = torch.ops.ofx.splat_points(
-            self._state, self._h.value, pts, _f32(normals, d, (P, 3)), a, _f32(weights, d, (P, 4)), v, packed,
-            [float(x) for x in intr[:4]], H, W, float(splat_radius), float(occl_margin))
+            self._state, self._h.value, pts, nrm, a, w, v, packed, [float(x) for x in intr[:4]], H, W,
+            float(splat_radius), float(occl_margin))
         out = {"depth": depth, "index": index, "code": code, "warped": warped, "visible": (code == 0).to(torch.uint8)}
         if normal_map:
             hit = index >= 0

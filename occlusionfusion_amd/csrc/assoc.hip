@@ -16,13 +16,14 @@
 //
 // One thread per point, a gather: trip 1 loads the point, its normal, anchors, weights and valid flag, trip 2 the four
 // 64-B node records (L2-resident), trip 3 the five vertex-map pixels once the pixel is known (neighbour coordinates are
-// clamped into the image, so the fifteen loads are unconditional and issue together). No LDS, no atomics. The accepted
+// clamped into the image, so the fifteen loads are unconditional and issue together); the three trips and the gates
+// are gate_device.h's, shared with rigid.hip and splat.hip. No LDS, no atomics. The accepted
 // points are ranked by scan_flags (ascending point index) and emitted in that order; more than max_matches of them are
 // thinned evenly and deterministically (rank r is kept iff floor((r+1)·max/n) > floor(r·max/n), 64-bit), where the
 // reference draws an unseeded randperm (model/model.py:319-334).
 #include "ofx_common.h"
+#include "gate_device.h"
 #include "scan_flags.h"
-#include "warp_device.h"
 
 namespace ofx {
 
@@ -32,10 +33,6 @@ struct Assoc {
   int32_t* rank = nullptr;   // [cap + 1] exclusive ranks of the accepted points, their number at [n]
   int32_t* tsum = nullptr;   // [scan_tiles(cap) + 1]
 };
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
 
 // VALID / NRM: valid / normals given (compile-time, so that trip 1 is branch-free)
 template <bool VALID, bool NRM>
@@ -50,84 +47,27 @@ __global__ __launch_bounds__(256) void k_assoc_gate(const float* __restrict__ pt
                                                      float* __restrict__ warped) {
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (p >= n) return;
-  // trip 1
-  float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
-  const int4 a4 = anchors[p];
-  const float4 w4 = weights[p];
-  bool ok = VALID ? valid[p] != 0 : true;
-  float nx = 0.f, ny = 0.f, nz = 0.f;
-  if (NRM) { nx = nrm[3 * p]; ny = nrm[3 * p + 1]; nz = nrm[3 * p + 2]; }
-  const int ids[4] = {a4.x, a4.y, a4.z, a4.w};
-  const float w[4] = {w4.x, w4.y, w4.z, w4.w};
-  // an anchor outside the graph cannot be gathered: such a point counts as invalid skin
-  ok = ok && (unsigned)ids[0] < (unsigned)n_nodes && (unsigned)ids[1] < (unsigned)n_nodes &&
-       (unsigned)ids[2] < (unsigned)n_nodes && (unsigned)ids[3] < (unsigned)n_nodes;
+  SkinPt s;
+  const bool ok = skin_load<VALID, NRM>(pts, nrm, anchors, weights, valid, n_nodes, p, 0.f, s);
   int cd = 1;
   float tx = 0.f, ty = 0.f, tz = 0.f;
   if (ok) {
-    // trip 2 (the normal's blend reads the same four records)
-    ed_warp(nodes, ids, w, 4, x, y, z);
-    if (NRM) {
-      ed_warp_normal(nodes, ids, w, 4, nx, ny, nz);
-      normalise3(nx, ny, nz);
-    }
-    const int64_t pix = (isfinite(x) && isfinite(y) && isfinite(z)) ? project_f32(c, x, y, z) : -1;
-    cd = 2;
-    if (pix >= 0) {
-      const int u = (int)(pix % c.W), v = (int)(pix / c.W);
-      const int64_t hw = (int64_t)c.H * c.W;
-      // trip 3
-      const int64_t il = (int64_t)v * c.W + max(u - 1, 0), ir = (int64_t)v * c.W + min(u + 1, c.W - 1);
-      const int64_t iu = (int64_t)max(v - 1, 0) * c.W + u, id = (int64_t)min(v + 1, c.H - 1) * c.W + u;
-      const float qx = vmap[pix], qy = vmap[hw + pix], qz = vmap[2 * hw + pix];
-      const float lx = vmap[il], ly = vmap[hw + il], lz = vmap[2 * hw + il];
-      const float rx = vmap[ir], ry = vmap[hw + ir], rz = vmap[2 * hw + ir];
-      const float ux = vmap[iu], uy = vmap[hw + iu], uz = vmap[2 * hw + iu];
-      const float dx = vmap[id], dy = vmap[hw + id], dz = vmap[2 * hw + id];
-      // all fifteen values in registers here: the loads leave together instead of sinking into the gates below
-      asm volatile("" :: "v"(qx), "v"(qy), "v"(qz), "v"(lx), "v"(ly), "v"(lz), "v"(rx), "v"(ry), "v"(rz), "v"(ux),
-                   "v"(uy), "v"(uz), "v"(dx), "v"(dy), "v"(dz));
-      const bool border = u == 0 || v == 0 || u == c.W - 1 || v == c.H - 1;
-      if (!(qz > 0.f)) {
-        cd = 3;
-      } else if (border || !(lz > 0.f && rz > 0.f && uz > 0.f && dz > 0.f) || fabsf(lz - qz) > edge_max ||
-                 fabsf(rz - qz) > edge_max || fabsf(uz - qz) > edge_max || fabsf(dz - qz) > edge_max) {
-        cd = 4;
+    skin_warp<NRM>(nodes, s);
+    GateHit h;
+    cd = proj_gate<NRM>(c, vmap, s, dist_max, cos_min, edge_max, h);
+    if (cd == 0) {
+      if (mode == OFX_ASSOC_PLANE) {
+        const float d = dot3(h.ex, h.ey, h.ez, h.nx, h.ny, h.nz);
+        tx = s.x + h.nx * d; ty = s.y + h.ny * d; tz = s.z + h.nz * d;
       } else {
-        const float ax = rx - lx, ay = ry - ly, az = rz - lz;
-        const float bx = dx - ux, by = dy - uy, bz = dz - uz;
-        float cx = ay * bz - az * by;
-        float cy = az * bx - ax * bz;
-        float cz = ax * by - ay * bx;
-        const float l2 = (cx * cx + cy * cy) + cz * cz;
-        cd = 4;
-        if (l2 > 0.f && isfinite(l2)) {
-          const float len = (float)sqrt((double)l2);
-          cx = cdiv(cx, len); cy = cdiv(cy, len); cz = cdiv(cz, len);
-          if (dot3(cx, cy, cz, qx, qy, qz) > 0.f) { cx = -cx; cy = -cy; cz = -cz; }
-          const float ex = qx - x, ey = qy - y, ez = qz - z;
-          const float d2 = (ex * ex + ey * ey) + ez * ez;
-          if (d2 > dist_max * dist_max) {
-            cd = 5;
-          } else if (NRM && dot3(nx, ny, nz, cx, cy, cz) < cos_min) {
-            cd = 6;
-          } else {
-            cd = 0;
-            if (mode == OFX_ASSOC_PLANE) {
-              const float s = dot3(ex, ey, ez, cx, cy, cz);
-              tx = x + cx * s; ty = y + cy * s; tz = z + cz * s;
-            } else {
-              tx = qx; ty = qy; tz = qz;
-            }
-          }
-        }
+        tx = h.qx; ty = h.qy; tz = h.qz;
       }
     }
   }
   code[p] = (uint8_t)cd;
   flag[p] = cd == 0 ? 1 : 0;
   tgt[3 * p] = tx; tgt[3 * p + 1] = ty; tgt[3 * p + 2] = tz;
-  if (warped) { warped[3 * p] = x; warped[3 * p + 1] = y; warped[3 * p + 2] = z; }
+  if (warped) { warped[3 * p] = s.x; warped[3 * p + 1] = s.y; warped[3 * p + 2] = s.z; }
 }
 
 __global__ __launch_bounds__(256) void k_assoc_emit(const uint8_t* __restrict__ flag, const int32_t* __restrict__ rank,
@@ -212,20 +152,18 @@ int ofx_associate(void* handle, const float* points, const float* normals, const
     OFX_HIP(hipMemsetAsync(count, 0, 2 * sizeof(int32_t), hs));
     return OFX_OK;
   }
-  OFX_CHECK_ARG(n_nodes >= 1, "bad n_nodes");
-  OFX_CHECK_ARG(points && anchors && weights && packed_nodes && point_image && code && tgt, "null buffer");
+  if (int st = check_skinned(points, anchors, weights, packed_nodes, n_nodes, point_image && code && tgt,
+                             (uintptr_t)anchors_out | (uintptr_t)weights_out))
+    return st;
   OFX_CHECK_ARG(prm->max_matches == 0 || (match_idx && src_out && tgt_out && anchors_out && weights_out),
                 "null compacted output");
-  OFX_CHECK_ARG((((uintptr_t)anchors | (uintptr_t)weights | (uintptr_t)anchors_out | (uintptr_t)weights_out |
-                  (uintptr_t)packed_nodes) & 15) == 0, "anchors / weights / node records must be 16-byte aligned");
   const unsigned grid = grid_for(n_points, 256, 1 << 30);
-  auto gate = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, hs, points, normals, (const int4*)anchors,
-                       (const float4*)weights, valid, (const float4*)packed_nodes, n_nodes, make_cam(cam), point_image,
-                       prm->dist_max, prm->cos_min, prm->edge_max, prm->mode, n_points, code, a->flag, tgt, warped);
-  };
-  if (valid) { if (normals) gate(k_assoc_gate<true, true>); else gate(k_assoc_gate<true, false>); }
-  else { if (normals) gate(k_assoc_gate<false, true>); else gate(k_assoc_gate<false, false>); }
+  dispatch_valid_nrm(valid, normals, [&](auto V, auto N) {
+    hipLaunchKernelGGL((k_assoc_gate<decltype(V)::value, decltype(N)::value>), dim3(grid), dim3(256), 0, hs, points,
+                       normals, (const int4*)anchors, (const float4*)weights, valid, (const float4*)packed_nodes,
+                       n_nodes, make_cam(cam), point_image, prm->dist_max, prm->cos_min, prm->edge_max, prm->mode,
+                       n_points, code, a->flag, tgt, warped);
+  });
   OFX_LAUNCH_CHECK();
   int st = scan_flags(a->flag, n_points, a->rank, a->tsum, hs);
   if (st) return st;

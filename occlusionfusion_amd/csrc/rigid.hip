@@ -4,9 +4,9 @@
 // stage of DynamicFusion). It has no reference twin (parity unpinned; restated op for op in tests/rigid_ref.py). One
 // iteration, per model point (f32, no contraction, every step fixed):
 //
-//   x', n' = ofx_associate's warped point and normalised warped normal (the shared warp_device.h code)
+//   x', n' = ofx_associate's warped point and normalised warped normal (gate_device.h: skin_load, skin_warp)
 //   y = Rf x' + tf, m = Rf n'      Rf, tf: the f32 roundings of the f64 pose; rows summed ((a0·x + a1·y) + a2·z) + t
-//   pixel, q, n_q, codes 1-6       ofx_associate's to the letter, with y and m in place of x' and n'
+//   pixel, q, n_q, codes 1-6       ofx_associate's (gate_device.h: proj_gate), with y and m in place of x' and n'
 //   accepted: e = q - y, r = e·n_q, c = y x n_q (a·b - c·d per component), row J = [c, n_q]
 //
 // k_rigid_gate (one thread per point, ofx_associate's three-trip gather) forms the 28 exact f64 products of the row
@@ -19,7 +19,7 @@
 // ceil(n / 256): the summation order depends on n_points alone. All iterations are enqueued at once; a device flag set
 // by a failed or converged iteration makes every later launch leave after one load.
 #include "ofx_common.h"
-#include "warp_device.h"
+#include "gate_device.h"
 
 namespace ofx {
 
@@ -30,10 +30,6 @@ struct Rigid {
   double* part = nullptr;    // [ceil(cap / 256)][kRigidRec] workgroup records
   int32_t* stop = nullptr;   // [1] non-zero: the remaining iterations drain
 };
-
-__device__ __forceinline__ float rdot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
-}
 
 // One halving step of the wave's transposed reduction: lanes l and l ^ off pair up; the one with the bit clear keeps
 // entries [0, N) and hands over [N, 2N), the other the reverse; each adds what it receives to what it keeps. N entries
@@ -81,87 +77,32 @@ __global__ __launch_bounds__(256) void k_rigid_gate(const float* __restrict__ pt
     for (int j = 0; j < 3; ++j) R[3 * i + j] = (float)pose[4 * i + j];
     t[i] = (float)pose[4 * i + 3];
   }
-  // trip 1
-  float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
-  const int4 a4 = anchors[p];
-  const float4 w4 = weights[p];
-  bool ok = VALID ? valid[p] != 0 : true;
-  float nx = 0.f, ny = 0.f, nz = 0.f;
-  if (NRM) { nx = nrm[3 * p]; ny = nrm[3 * p + 1]; nz = nrm[3 * p + 2]; }
-  const int ids[4] = {a4.x, a4.y, a4.z, a4.w};
-  const float w[4] = {w4.x, w4.y, w4.z, w4.w};
-  // an anchor outside the graph cannot be gathered: such a point counts as invalid skin
-  ok = ok && (unsigned)ids[0] < (unsigned)n_nodes && (unsigned)ids[1] < (unsigned)n_nodes &&
-       (unsigned)ids[2] < (unsigned)n_nodes && (unsigned)ids[3] < (unsigned)n_nodes;
+  SkinPt s;
+  const bool ok = skin_load<VALID, NRM>(pts, nrm, anchors, weights, valid, n_nodes, p, 0.f, s);
   int cd = 1;
   float J[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, r = 0.f;
   if (ok) {
-    // trip 2 (the normal's blend reads the same four records)
-    ed_warp(nodes, ids, w, 4, x, y, z);
+    skin_warp<NRM>(nodes, s);
     {
-      const float yx = ((R[0] * x + R[1] * y) + R[2] * z) + t[0];
-      const float yy = ((R[3] * x + R[4] * y) + R[5] * z) + t[1];
-      const float yz = ((R[6] * x + R[7] * y) + R[8] * z) + t[2];
-      x = yx; y = yy; z = yz;
+      const float yx = ((R[0] * s.x + R[1] * s.y) + R[2] * s.z) + t[0];
+      const float yy = ((R[3] * s.x + R[4] * s.y) + R[5] * s.z) + t[1];
+      const float yz = ((R[6] * s.x + R[7] * s.y) + R[8] * s.z) + t[2];
+      s.x = yx; s.y = yy; s.z = yz;
     }
     if (NRM) {
-      ed_warp_normal(nodes, ids, w, 4, nx, ny, nz);
-      normalise3(nx, ny, nz);
-      const float mx = (R[0] * nx + R[1] * ny) + R[2] * nz;
-      const float my = (R[3] * nx + R[4] * ny) + R[5] * nz;
-      const float mz = (R[6] * nx + R[7] * ny) + R[8] * nz;
-      nx = mx; ny = my; nz = mz;
+      const float mx = (R[0] * s.nx + R[1] * s.ny) + R[2] * s.nz;
+      const float my = (R[3] * s.nx + R[4] * s.ny) + R[5] * s.nz;
+      const float mz = (R[6] * s.nx + R[7] * s.ny) + R[8] * s.nz;
+      s.nx = mx; s.ny = my; s.nz = mz;
     }
-    const int64_t pix = (isfinite(x) && isfinite(y) && isfinite(z)) ? project_f32(c, x, y, z) : -1;
-    cd = 2;
-    if (pix >= 0) {
-      const int u = (int)(pix % c.W), v = (int)(pix / c.W);
-      const int64_t hw = (int64_t)c.H * c.W;
-      // trip 3
-      const int64_t il = (int64_t)v * c.W + max(u - 1, 0), ir = (int64_t)v * c.W + min(u + 1, c.W - 1);
-      const int64_t iu = (int64_t)max(v - 1, 0) * c.W + u, id = (int64_t)min(v + 1, c.H - 1) * c.W + u;
-      const float qx = vmap[pix], qy = vmap[hw + pix], qz = vmap[2 * hw + pix];
-      const float lx = vmap[il], ly = vmap[hw + il], lz = vmap[2 * hw + il];
-      const float rx = vmap[ir], ry = vmap[hw + ir], rz = vmap[2 * hw + ir];
-      const float ux = vmap[iu], uy = vmap[hw + iu], uz = vmap[2 * hw + iu];
-      const float dx = vmap[id], dy = vmap[hw + id], dz = vmap[2 * hw + id];
-      // all fifteen values in registers here: the loads leave together instead of sinking into the gates below
-      asm volatile("" :: "v"(qx), "v"(qy), "v"(qz), "v"(lx), "v"(ly), "v"(lz), "v"(rx), "v"(ry), "v"(rz), "v"(ux),
-                   "v"(uy), "v"(uz), "v"(dx), "v"(dy), "v"(dz));
-      const bool border = u == 0 || v == 0 || u == c.W - 1 || v == c.H - 1;
-      if (!(qz > 0.f)) {
-        cd = 3;
-      } else if (border || !(lz > 0.f && rz > 0.f && uz > 0.f && dz > 0.f) || fabsf(lz - qz) > edge_max ||
-                 fabsf(rz - qz) > edge_max || fabsf(uz - qz) > edge_max || fabsf(dz - qz) > edge_max) {
-        cd = 4;
-      } else {
-        const float ax = rx - lx, ay = ry - ly, az = rz - lz;
-        const float bx = dx - ux, by = dy - uy, bz = dz - uz;
-        float cx = ay * bz - az * by;
-        float cy = az * bx - ax * bz;
-        float cz = ax * by - ay * bx;
-        const float l2 = (cx * cx + cy * cy) + cz * cz;
-        cd = 4;
-        if (l2 > 0.f && isfinite(l2)) {
-          const float len = (float)sqrt((double)l2);
-          cx = cdiv(cx, len); cy = cdiv(cy, len); cz = cdiv(cz, len);
-          if (rdot3(cx, cy, cz, qx, qy, qz) > 0.f) { cx = -cx; cy = -cy; cz = -cz; }
-          const float ex = qx - x, ey = qy - y, ez = qz - z;
-          const float d2 = (ex * ex + ey * ey) + ez * ez;
-          if (d2 > dist_max * dist_max) {
-            cd = 5;
-          } else if (NRM && rdot3(nx, ny, nz, cx, cy, cz) < cos_min) {
-            cd = 6;
-          } else {
-            cd = 0;
-            r = rdot3(ex, ey, ez, cx, cy, cz);
-            J[0] = y * cz - z * cy;
-            J[1] = z * cx - x * cz;
-            J[2] = x * cy - y * cx;
-            J[3] = cx; J[4] = cy; J[5] = cz;
-          }
-        }
-      }
+    GateHit h;
+    cd = proj_gate<NRM>(c, vmap, s, dist_max, cos_min, edge_max, h);
+    if (cd == 0) {
+      r = dot3(h.ex, h.ey, h.ez, h.nx, h.ny, h.nz);
+      J[0] = s.y * h.nz - s.z * h.ny;
+      J[1] = s.z * h.nx - s.x * h.nz;
+      J[2] = s.x * h.ny - s.y * h.nx;
+      J[3] = h.nx; J[4] = h.ny; J[5] = h.nz;
     }
   }
   if (in && code) code[p] = (uint8_t)cd;
@@ -384,21 +325,16 @@ int ofx_rigid_icp(void* handle, const float* points, const float* normals, const
     OFX_LAUNCH_CHECK();
     return OFX_OK;
   }
-  OFX_CHECK_ARG(n_nodes >= 1, "bad n_nodes");
-  OFX_CHECK_ARG(points && anchors && weights && packed_nodes && point_image, "null buffer");
-  OFX_CHECK_ARG((((uintptr_t)anchors | (uintptr_t)weights | (uintptr_t)packed_nodes) & 15) == 0,
-                "anchors / weights / node records must be 16-byte aligned");
+  if (int st = check_skinned(points, anchors, weights, packed_nodes, n_nodes, point_image != nullptr)) return st;
   OFX_HIP(hipMemsetAsync(a->stop, 0, sizeof(int32_t), hs));
   const unsigned grid = (unsigned)((n_points + 255) / 256);
-  auto gate = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, hs, points, normals, (const int4*)anchors,
-                       (const float4*)weights, valid, (const float4*)packed_nodes, n_nodes, make_cam(cam), point_image,
-                       prm->dist_max, prm->cos_min, prm->edge_max, n_points, (const double*)pose,
-                       (const int32_t*)a->stop, code, a->part);
-  };
   for (int it = 0; it < prm->iters; ++it) {
-    if (valid) { if (normals) gate(k_rigid_gate<true, true>); else gate(k_rigid_gate<true, false>); }
-    else { if (normals) gate(k_rigid_gate<false, true>); else gate(k_rigid_gate<false, false>); }
+    dispatch_valid_nrm(valid, normals, [&](auto V, auto N) {
+      hipLaunchKernelGGL((k_rigid_gate<decltype(V)::value, decltype(N)::value>), dim3(grid), dim3(256), 0, hs, points,
+                         normals, (const int4*)anchors, (const float4*)weights, valid, (const float4*)packed_nodes,
+                         n_nodes, make_cam(cam), point_image, prm->dist_max, prm->cos_min, prm->edge_max, n_points,
+                         (const double*)pose, (const int32_t*)a->stop, code, a->part);
+    });
     OFX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_rigid_solve, dim3(1), dim3(1024), 0, hs, (const double*)a->part, (int64_t)grid,
                        prm->min_matches, prm->damping, prm->stop_twist, pose, a->stop,

@@ -6,8 +6,8 @@
 // iteration. Here the model is already a set of skinned, oriented surface points (ofx_surface_points), so the live view
 // is a z-buffer of their discs (no reference twin, parity unpinned; restated op for op in tests/splat_ref.py):
 //
-//   x', n' = ofx_associate's warped point and normalised warped normal     (warp_device.h: the same bits)
-//   (u, v) = pixel of x'                                                   (project_f32)
+//   x', n' = ofx_associate's warped point and normalised warped normal     (gate_device.h: the same bits)
+//   (u, v) = pixel of x'                                                   (gate_device.h: pixel_of)
 //   codes, first that applies: 1 invalid skin, 2 non-finite / behind the camera / off the image, 3 back-facing
 //   (!(s < 0), s = n'.x'); then 4 occluded ((z' - depth[v,u]) > occl_margin) or 0 visible, once the buffer is complete
 //   footprint of a live point: |du| <= ru, |dv| <= rv, r = clamp(ceil(f*rho / z'), 0, OFX_SPLAT_RMAX); the centre pixel
@@ -21,7 +21,7 @@
 // trip 1 the point, its normal, anchors, weights and valid flag, trip 2 the four node records, then the footprint loop
 // of no-return atomics) and k_splat_resolve (one grid over the pixels and then the points).
 #include "ofx_common.h"
-#include "warp_device.h"
+#include "gate_device.h"
 
 namespace ofx {
 
@@ -55,26 +55,13 @@ __global__ __launch_bounds__(256) void k_splat(const float* __restrict__ pts, co
                                                 float* __restrict__ warped_n) {
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (p >= n) return;
-  // trip 1
-  float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
-  const int4 a4 = anchors[p];
-  const float4 w4 = weights[p];
-  bool ok = VALID ? valid[p] != 0 : true;
-  float nx = 0.f, ny = 0.f, nz = -1.f;
-  if (NRM) { nx = nrm[3 * p]; ny = nrm[3 * p + 1]; nz = nrm[3 * p + 2]; }
-  const int ids[4] = {a4.x, a4.y, a4.z, a4.w};
-  const float w[4] = {w4.x, w4.y, w4.z, w4.w};
-  ok = ok && (unsigned)ids[0] < (unsigned)n_nodes && (unsigned)ids[1] < (unsigned)n_nodes &&
-       (unsigned)ids[2] < (unsigned)n_nodes && (unsigned)ids[3] < (unsigned)n_nodes;
+  SkinPt sk;
+  const bool ok = skin_load<VALID, NRM>(pts, nrm, anchors, weights, valid, n_nodes, p, -1.f, sk);   // no normal: (0, 0, -1)
+  float &x = sk.x, &y = sk.y, &z = sk.z, &nx = sk.nx, &ny = sk.ny, &nz = sk.nz;
   int32_t pix32 = -1;
   if (ok) {
-    // trip 2 (the normal's blend reads the same four records)
-    ed_warp(nodes, ids, w, 4, x, y, z);
-    if (NRM) {
-      ed_warp_normal(nodes, ids, w, 4, nx, ny, nz);
-      normalise3(nx, ny, nz);
-    }
-    const int64_t pix = (isfinite(x) && isfinite(y) && isfinite(z)) ? project_f32(c, x, y, z) : -1;
+    skin_warp<NRM>(nodes, sk);
+    const int64_t pix = pixel_of(c, x, y, z);
     pix32 = -2;
     if (pix >= 0) {
       const float s = (nx * x + ny * y) + nz * z;
@@ -199,18 +186,14 @@ int ofx_splat_points(void* handle, const float* points, const float* normals, co
   hipLaunchKernelGGL(k_splat_clear, dim3(grid_for(n_pix, 256, 1 << 30)), dim3(256), 0, hs, h->zbuf, n_pix);
   OFX_LAUNCH_CHECK();
   if (n_points > 0) {
-    OFX_CHECK_ARG(n_nodes >= 1, "bad n_nodes");
-    OFX_CHECK_ARG(points && anchors && weights && packed_nodes, "null buffer");
-    OFX_CHECK_ARG((((uintptr_t)anchors | (uintptr_t)weights | (uintptr_t)packed_nodes) & 15) == 0,
-                  "anchors / weights / node records must be 16-byte aligned");
+    if (int st = check_skinned(points, anchors, weights, packed_nodes, n_nodes)) return st;
     const unsigned grid = grid_for(n_points, 256, 1 << 30);
-    auto splat = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, hs, points, normals, (const int4*)anchors,
-                         (const float4*)weights, valid, (const float4*)packed_nodes, n_nodes, make_cam(cam),
-                         prm->splat_radius, n_points, h->zbuf, h->ppix, h->pz, warped, warped_normals);
-    };
-    if (valid) { if (normals) splat(k_splat<true, true>); else splat(k_splat<true, false>); }
-    else { if (normals) splat(k_splat<false, true>); else splat(k_splat<false, false>); }
+    dispatch_valid_nrm(valid, normals, [&](auto V, auto N) {
+      hipLaunchKernelGGL((k_splat<decltype(V)::value, decltype(N)::value>), dim3(grid), dim3(256), 0, hs, points,
+                         normals, (const int4*)anchors, (const float4*)weights, valid, (const float4*)packed_nodes,
+                         n_nodes, make_cam(cam), prm->splat_radius, n_points, h->zbuf, h->ppix, h->pz, warped,
+                         warped_normals);
+    });
     OFX_LAUNCH_CHECK();
   }
   if (depth || index || (code && n_points > 0)) {

@@ -46,25 +46,32 @@ def pixel_f32(points, intr, H, W):
     return inside, np.where(inside, u, 0).astype(np.int64), np.where(inside, v, 0).astype(np.int64)
 
 
-def gate(points, normals, anchors, weights, valid, node_R, node_T, nodes, intr, point_image, dist_max=0.05,
-         cos_min=0.5, edge_max=0.03, mode=PLANE):
-    """Per point: (code u8[P], tgt f32[P,3], warped f32[P,3]). point_image: (3, H, W) f32 vertex map."""
+def warp_skinned(points, normals, anchors, weights, valid, node_R, node_T, nodes):
+    """Trips 1 and 2 -> (ok bool[P]: valid skin with every anchor inside the graph, warped f32[P,3], warped unit normals
+    f32[P,3] or None). Invalid points keep x (ofx_deform_points)."""
     x = np.ascontiguousarray(points, F32).reshape(-1, 3)
     P = x.shape[0]
     a = np.asarray(anchors, np.int32).reshape(P, 4)
     w = np.asarray(weights, F32).reshape(P, 4)
     N = np.asarray(nodes).reshape(-1, 3).shape[0]
+    ok = np.ones(P, bool) if valid is None else np.asarray(valid).reshape(P) != 0
+    ok = ok & ((a >= 0) & (a < N)).all(1)                        # an anchor outside the graph cannot be gathered
+    warped = fo.ed_warp(x, a, w, ok, node_R, node_T, nodes)
+    with np.errstate(all="ignore"):
+        nw = warp_normals(normals, np.where(ok[:, None], a, 0), w, node_R) if normals is not None else None
+    return ok, warped, nw
+
+
+def project_gate(ok, y, m, intr, point_image, dist_max=0.05, cos_min=0.5, edge_max=0.03):
+    """The gate of camera-space points y f32[P,3] with unit normals m (None: no cosine gate), from the pixel to the
+    cosine gate; the points outside ok get code 1 -> (code u8[P], live = code == 0, q, nq, e): the target vertex, its
+    normal towards the camera and q - y, f32[P,3], meaningful where live. point_image: (3, H, W) f32 vertex map."""
     vm = np.asarray(point_image, F32)
     _, H, W = vm.shape
     dist_max, cos_min, edge_max = F32(dist_max), F32(cos_min), F32(edge_max)
-    ok = np.ones(P, bool) if valid is None else np.asarray(valid).reshape(P) != 0
-    ok = ok & ((a >= 0) & (a < N)).all(1)                        # an anchor outside the graph cannot be gathered
     code = np.where(ok, 0, 1).astype(np.uint8)
-    warped = fo.ed_warp(x, a, w, ok, node_R, node_T, nodes)    # invalid points keep x (ofx_deform_points)
-    tgt = np.zeros((P, 3), F32)
     with np.errstate(all="ignore"):
-        nw = warp_normals(normals, np.where(ok[:, None], a, 0), w, node_R) if normals is not None else None
-        inside, u, v = pixel_f32(warped, intr, H, W)
+        inside, u, v = pixel_f32(y, intr, H, W)
         code[ok & ~inside] = 2
         live = ok & inside
         q = vm[:, v, u].T                                         # (P, 3)
@@ -84,22 +91,28 @@ def gate(points, normals, anchors, weights, valid, node_R, node_T, nodes, intr, 
         live &= ~no_normal
         nq = (c / np.sqrt(l2)[:, None]).astype(F32)
         nq = np.where((_dot(nq, q) > 0)[:, None], -nq, nq)
-        e = q - warped
+        e = q - y
         d2 = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
         far = d2 > dist_max * dist_max
         code[live & far] = 5
         live &= ~far
-        if nw is not None:
-            away = _dot(nw, nq) < cos_min
+        if m is not None:
+            away = _dot(m, nq) < cos_min
             code[live & away] = 6
             live &= ~away
-        if mode == PLANE:
-            s = _dot(e, nq)
-            t = warped + nq * s[:, None]
-        else:
-            t = q
-    tgt[live] = t[live]
     assert np.array_equal(live, code == 0)
+    return code, live, q, nq, e
+
+
+def gate(points, normals, anchors, weights, valid, node_R, node_T, nodes, intr, point_image, dist_max=0.05,
+         cos_min=0.5, edge_max=0.03, mode=PLANE):
+    """Per point: (code u8[P], tgt f32[P,3], warped f32[P,3]): the gate, then the target rule of an accepted point."""
+    ok, warped, nw = warp_skinned(points, normals, anchors, weights, valid, node_R, node_T, nodes)
+    code, live, q, nq, e = project_gate(ok, warped, nw, intr, point_image, dist_max, cos_min, edge_max)
+    with np.errstate(all="ignore"):
+        t = warped + nq * _dot(e, nq)[:, None] if mode == PLANE else q
+    tgt = np.zeros(warped.shape, F32)
+    tgt[live] = t[live]
     return code, tgt, warped
 
 

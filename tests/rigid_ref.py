@@ -4,7 +4,7 @@ Rigid point-to-plane ICP has no reference twin, so this file is what the kernel 
 f32, one operation per rounding in the kernel's order (the library is compiled without contraction): codes, rows J and
 residuals r are reproduced bit for bit. The normal equations are the correctly rounded sums (math.fsum) of the exact f64
 products; the kernel's fixed-order f64 sums differ from them by the summation error only. The solve and the pose update
-are f64. The warp, the pixel and the target-normal code are assoc_ref's / the oracle's.
+are f64. The warp and the whole gate from the pixel to the cosine test are assoc_ref's / the oracle's.
 """
 import math
 import os
@@ -34,62 +34,22 @@ def _rigid_rows(R, t, x):
 
 def rows(points, normals, anchors, weights, valid, node_R, node_T, nodes, intr, point_image, pose, dist_max=0.05,
          cos_min=0.5, edge_max=0.03):
-    """One iteration's per-point part: (code u8[P], J f32[P,6], r f32[P]); J and r are zero where code != 0."""
-    x = np.ascontiguousarray(points, F32).reshape(-1, 3)
-    P = x.shape[0]
-    a = np.asarray(anchors, np.int32).reshape(P, 4)
-    w = np.asarray(weights, F32).reshape(P, 4)
-    N = np.asarray(nodes).reshape(-1, 3).shape[0]
-    vm = np.asarray(point_image, F32)
-    _, H, W = vm.shape
+    """One iteration's per-point part: (code u8[P], J f32[P,6], r f32[P]); J and r are zero where code != 0. The
+    association's gate (assoc_ref.project_gate) with y = Rf x' + tf and m = Rf n' in place of x' and n'."""
     pose = np.asarray(pose, np.float64).reshape(3, 4)
     Rf, tf = pose[:, :3].astype(F32), pose[:, 3].astype(F32)
-    dist_max, cos_min, edge_max = F32(dist_max), F32(cos_min), F32(edge_max)
-    ok = np.ones(P, bool) if valid is None else np.asarray(valid).reshape(P) != 0
-    ok = ok & ((a >= 0) & (a < N)).all(1)
-    code = np.where(ok, 0, 1).astype(np.uint8)
+    ok, warped, nw = ar.warp_skinned(points, normals, anchors, weights, valid, node_R, node_T, nodes)
+    P = warped.shape[0]
     J, r = np.zeros((P, 6), F32), np.zeros(P, F32)
     if P == 0:
-        return code, J, r
-    warped = fo.ed_warp(x, a, w, ok, node_R, node_T, nodes)
+        return np.zeros(0, np.uint8), J, r
     with np.errstate(all="ignore"):
         y = _rigid_rows(Rf, tf, warped)
-        m = None
-        if normals is not None:
-            m = _rigid_rows(Rf, None, ar.warp_normals(normals, np.where(ok[:, None], a, 0), w, node_R))
-        inside, u, v = ar.pixel_f32(y, intr, H, W)
-        code[ok & ~inside] = 2
-        live = ok & inside
-        q = vm[:, v, u].T
-        code[live & ~(q[:, 2] > 0)] = 3
-        live &= q[:, 2] > 0
-        border = (u == 0) | (v == 0) | (u == W - 1) | (v == H - 1)
-        ul, ur, vu, vd = np.maximum(u - 1, 0), np.minimum(u + 1, W - 1), np.maximum(v - 1, 0), np.minimum(v + 1, H - 1)
-        ql, qr, qu, qd = vm[:, v, ul].T, vm[:, v, ur].T, vm[:, vu, u].T, vm[:, vd, u].T
-        zs = np.stack([ql[:, 2], qr[:, 2], qu[:, 2], qd[:, 2]], 1)
-        no_normal = border | ~(zs > 0).all(1) | (np.abs(zs - q[:, 2:3]) > edge_max).any(1)
-        A, B = qr - ql, qd - qu
-        c = np.stack([A[:, 1] * B[:, 2] - A[:, 2] * B[:, 1], A[:, 2] * B[:, 0] - A[:, 0] * B[:, 2],
-                      A[:, 0] * B[:, 1] - A[:, 1] * B[:, 0]], 1)
-        l2 = (c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]
-        no_normal |= ~((l2 > 0) & np.isfinite(l2))
-        code[live & no_normal] = 4
-        live &= ~no_normal
-        nq = (c / np.sqrt(l2)[:, None]).astype(F32)
-        nq = np.where((ar._dot(nq, q) > 0)[:, None], -nq, nq)
-        e = q - y
-        d2 = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
-        far = d2 > dist_max * dist_max
-        code[live & far] = 5
-        live &= ~far
-        if m is not None:
-            away = ar._dot(m, nq) < cos_min
-            code[live & away] = 6
-            live &= ~away
+        m = _rigid_rows(Rf, None, nw) if nw is not None else None
+        code, live, _, nq, e = ar.project_gate(ok, y, m, intr, point_image, dist_max, cos_min, edge_max)
         res = ar._dot(e, nq)
         cr = np.stack([y[:, 1] * nq[:, 2] - y[:, 2] * nq[:, 1], y[:, 2] * nq[:, 0] - y[:, 0] * nq[:, 2],
                        y[:, 0] * nq[:, 1] - y[:, 1] * nq[:, 0]], 1)
-    assert np.array_equal(live, code == 0)
     J[live, :3], J[live, 3:], r[live] = cr[live], nq[live], res[live]
     return code, J, r
 

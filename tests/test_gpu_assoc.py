@@ -83,13 +83,14 @@ def scene(cuda):
     return s
 
 
-def _ref(s, mode, normals, max_matches, n=None):
-    """The restatement's outputs, its gate computed once per (mode, normals, n) and shared (never modified)."""
-    key = (mode, normals, n)
+def _ref(s, mode, normals, max_matches, n=None, valid=True):
+    """The restatement's outputs, its gate computed once per (mode, normals, n, valid) and shared (never modified)."""
+    key = (mode, normals, n, valid)
     if key not in s["ref"]:
         sl = slice(0, n)
         s["ref"][key] = ar.gate(s["pts"][sl], s["nrm"][sl] if normals else None, s["anchors"][sl], s["weights"][sl],
-                                s["valid"][sl], s["R"], s["T"], s["nodes"], INTR, s["vmap"], mode=mode, **PRM)
+                                s["valid"][sl] if valid else None, s["R"], s["T"], s["nodes"], INTR, s["vmap"],
+                                mode=mode, **PRM)
     code, tgt, warped = s["ref"][key]
     acc = np.nonzero(code == 0)[0]
     idx = acc[ar.emitted_ranks(acc.shape[0], max_matches)].astype(np.int32)
@@ -108,8 +109,9 @@ class _Handle:
         _lib.lib.ofx_assoc_destroy(self.h)
 
 
-def _direct(handle, d, mode, normals, max_matches, n=None, fill=0):
-    """ofx_associate through ctypes on the first n points; compacted buffers prefilled with `fill`."""
+def _direct(handle, d, mode, normals, max_matches, n=None, fill=0, valid=True):
+    """ofx_associate through ctypes on the first n points (valid=False: a NULL valid); compacted buffers prefilled with
+    `fill`."""
     dev = d["pts"].device
     n = d["pts"].shape[0] if n is None else n
     M = max_matches
@@ -123,7 +125,8 @@ def _direct(handle, d, mode, normals, max_matches, n=None, fill=0):
     cam = _lib.Camera(*INTR, W, H)
     prm = _lib.AssocParams(PRM["dist_max"], PRM["cos_min"], PRM["edge_max"], mode, M, 0)
     call("ofx_associate", handle.h, ptr(d["pts"]), ptr(d["nrm"]) if normals else None, ptr(d["anchors"]),
-         ptr(d["weights"]), ptr(d["valid"]), n, ptr(d["packed"]), d["packed"].shape[0], byref(cam), ptr(d["vmap"]), H, W,
+         ptr(d["weights"]), ptr(d["valid"]) if valid else None, n, ptr(d["packed"]), d["packed"].shape[0], byref(cam),
+         ptr(d["vmap"]), H, W,
          byref(prm), ptr(code), ptr(tgt), ptr(warped), ptr(midx), ptr(src_o), ptr(tgt_o), ptr(a_o), ptr(w_o), ptr(count),
          stream_ptr())
     return code, tgt, warped, midx, src_o, tgt_o, a_o, w_o, count
@@ -155,22 +158,29 @@ def test_scene_reaches_every_code(scene):
     assert np.bincount(_ref(scene, ar.POINT, False, 10)["code"], minlength=7)[6] == 0
 
 
-@pytest.mark.parametrize("mm", ["above", "exact", "below"])
-@pytest.mark.parametrize("normals", [True, False])
-@pytest.mark.parametrize("mode", [ar.POINT, ar.PLANE])
-def test_kernel_equals_restatement(scene, mode, normals, mm):
-    n_acc = int(_ref(scene, mode, normals, 0)["count"][0])
+# every (mode, normals, mm) with valid given, and valid = NULL (the kernels' VALID = false) in plane mode, thinned
+_KERNEL_CASES = [pytest.param(mode, normals, mm, True, id=f"{mode}-{normals}-{mm}") for mm in ("above", "exact", "below")
+                 for normals in (True, False) for mode in (ar.POINT, ar.PLANE)]
+_KERNEL_CASES += [pytest.param(ar.PLANE, normals, "below", False, id=f"{ar.PLANE}-{normals}-below-NULL")
+                  for normals in (True, False)]
+
+
+@pytest.mark.parametrize("mode,normals,mm,valid", _KERNEL_CASES)
+def test_kernel_equals_restatement(scene, mode, normals, mm, valid):
+    n_acc = int(_ref(scene, mode, normals, 0, valid=valid)["count"][0])
     assert n_acc > 1000
     M = {"above": n_acc + 5, "exact": n_acc, "below": 1000}[mm]
-    ref = _ref(scene, mode, normals, M)
+    ref = _ref(scene, mode, normals, M, valid=valid)
     assert ref["count"].tolist() == [n_acc, min(n_acc, M)]
-    out = _direct(_Handle(P_FULL), scene["dev"], mode, normals, M, fill=-3)
+    assert valid or (ref["code"] == 1).sum() < (scene["valid"] == 0).sum()   # the rows marked invalid are gated now
+    out = _direct(_Handle(P_FULL), scene["dev"], mode, normals, M, fill=-3, valid=valid)
     _assert_equals_ref(out, ref, fill=-3)
 
 
-@pytest.mark.parametrize("n", [1, 0, 4096, 4097])
+@pytest.mark.parametrize("n", [1, 0, 257, 4096, 4097])
 def test_small_and_tile_edge_sizes(scene, n):
-    """P = 1 and P = 0 (count [0, 0], nothing touched), and one full scan tile with and without a ragged flag."""
+    """P = 1 and P = 0 (count [0, 0], nothing touched), one full workgroup and a lone thread in the next, and one full
+    scan tile with and without a ragged flag."""
     h = _Handle(P_FULL)
     for M in (3, 5000):
         ref = _ref(scene, ar.PLANE, True, M, n=n)

@@ -44,8 +44,9 @@ def _dev(cuda, **arrays):
     return {k: None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(cuda) for k, v in arrays.items()}
 
 
-def _direct(handle, d, intr, H, W, rho=RHO, margin=MARGIN, normals=True, n=None, outputs="dickn"):
-    """ofx_splat_points through ctypes on the first n points; outputs prefilled, those not in `outputs` passed as NULL."""
+def _direct(handle, d, intr, H, W, rho=RHO, margin=MARGIN, normals=True, n=None, outputs="dickn", valid=True):
+    """ofx_splat_points through ctypes on the first n points (valid=False: a NULL valid); outputs prefilled, those not in
+    `outputs` passed as NULL."""
     dev = d["packed"].device
     n = d["pts"].shape[0] if n is None else n
     depth = torch.full((H, W), 7.0, device=dev)
@@ -56,7 +57,7 @@ def _direct(handle, d, intr, H, W, rho=RHO, margin=MARGIN, normals=True, n=None,
     prm = _lib.SplatParams(rho, margin)
     use = lambda c, t: ptr(t) if c in outputs else None   # noqa: E731
     call("ofx_splat_points", handle.h, ptr(d["pts"]), ptr(d["nrm"]) if normals else None, ptr(d["anchors"]),
-         ptr(d["weights"]), ptr(d.get("valid")), n, ptr(d["packed"]), d["packed"].shape[0], byref(cam), byref(prm),
+         ptr(d["weights"]), ptr(d.get("valid")) if valid else None, n, ptr(d["packed"]), d["packed"].shape[0], byref(cam), byref(prm),
          use("d", depth), use("i", index), use("c", code), use("k", warped), use("n", wn) if normals else None,
          stream_ptr())
     return depth, index, code, warped, wn
@@ -104,15 +105,21 @@ def two(cuda):
     return sc
 
 
-@pytest.mark.parametrize("normals", [True, False])
-def test_kernel_equals_restatement_on_the_two_layers(two, normals):
-    ref = two["ref"][normals]
+@pytest.mark.parametrize("normals,valid", [pytest.param(True, True, id="True"), pytest.param(False, True, id="False"),
+                                           pytest.param(True, False, id="True-NULL"),
+                                           pytest.param(False, False, id="False-NULL")])
+def test_kernel_equals_restatement_on_the_two_layers(two, normals, valid):
+    """valid given, and valid = NULL (the kernel's VALID = false): then only the anchor outside the graph is invalid."""
+    ref = two["ref"][normals] if valid else sp.splat(
+        two["points"], two["normals"] if normals else None, two["anchors_bad"], two["weights"], None, two["R"], two["T"],
+        two["nodes"], two["intr"], two["H"], two["W"], RHO, MARGIN)
     hist = np.bincount(ref["code"], minlength=5)
     print("codes 0..4:", hist.tolist(), "covered pixels:", int((ref["depth"] > 0).sum()))
-    assert hist[0] > 5000 and hist[1] > 100 and hist[4] > 500
+    assert hist[0] > 5000 and (hist[1] > 100 if valid else hist[1] == 1) and hist[4] > 500
     P = two["points"].shape[0]
     assert P % 256 != 0 and P > 256
-    out = _direct(_Handle(P, two["H"] * two["W"]), two["dev"], two["intr"], two["H"], two["W"], normals=normals)
+    out = _direct(_Handle(P, two["H"] * two["W"]), two["dev"], two["intr"], two["H"], two["W"], normals=normals,
+                  valid=valid)
     _assert_equals_ref(out, ref, normals)
     if not normals:
         assert torch.all(out[4] == 7.0)                     # warped_normals is not touched without normals
