@@ -47,6 +47,9 @@
  *                           point — (no reference twin: the reference renders the live model from a warped marching-
  *                           cubes mesh, tsdf.get_deformed_model and NonRigidICP/model/point_render.py. Parity unpinned;
  *                           restated op for op by tests/splat_ref.py)
+ *   ofx_prepare_depth       (new) bilateral-filtered depth of a frame, its vertex map and its normal map: what the depth
+ *                           tracker reads the live frame through — (no reference twin: the reference has no depth filter.
+ *                           Parity unpinned; restated op for op by tests/prepare_ref.py)
  *   ofx_depth_to_pc         Registration.optimize target cloud: depth_2_pc, NonRigidICP/model/geometry.py:44-59,
  *                           mask compaction, map_pixel_to_pcd              registration_fusion.py:104-109,388-395
  *   ofx_pixel_anchors_euclidean  csrc compute_pixel_anchors_euclidean     csrc/cpu/graph_proc.cpp:610-709
@@ -433,6 +436,44 @@ int ofx_splat_points(void* handle, const float* points, const float* normals, co
                      const uint8_t* valid, int64_t n_points, const float* packed_nodes, int32_t n_nodes,
                      const ofx_camera* cam, const ofx_splat_params* prm, float* depth, int32_t* index, uint8_t* code,
                      float* warped, float* warped_normals, ofx_stream_t s);
+
+/* ---------------- Depth-frame preparation: bilateral filter, vertex map, normal map (new capability; the reference has none —
+ * parity unpinned) ----------------
+ * What the tracker reads a live frame through, in place of ofx_backproject_depth of the raw image: the bilateral-filtered
+ * depth, its vertex map and the gate's target normal at every pixel. The integrate keeps reading the raw frame. Restated op
+ * for op by tests/prepare_ref.py. Per pixel (f32, no contraction, every step fixed):
+ *   D    = the depth in metres: f32 as given (is_u16 = 0) or u16 / normalizer, correctly rounded (is_u16 = 1:
+ *          ofx_backproject_depth's expression)
+ *   hole: !(D_c > 0) (a NaN included) writes 0 to every output
+ *   taps: dv = -radius..radius (outer), du = -radius..radius (inner); the tap N = D[v + dv, u + du] is skipped when it lies
+ *          outside the image, when !(N > 0), or when fabsf(diff) > range_cut with diff = N - D_c in f32 — a skipped tap
+ *          behaves exactly like a hole, so nothing bleeds across a depth edge
+ *   ws   = f32(exp(a_s * f64(du*du + dv*dv))), a_s = -0.5 / (f64(sigma_s) * f64(sigma_s))   (a host table)
+ *   wr   = f32(exp(a_r * (f64(diff) * f64(diff)))), a_r = -0.5 / (f64(sigma_r) * f64(sigma_r))
+ *   w    = ws * wr; num = num + w * N; den = den + w (f32, from zero, in tap order)
+ *   depth_out = num / den, correctly rounded. The centre tap (du = dv = 0) is always taken with w = 1 exactly — what the
+ *          formulas give for diff = 0, and held for a +inf centre, whose own diff would be inf - inf — so den >= 1 and radius
+ *          0 returns D_c exactly.
+ *   point_image = ofx_backproject_depth's vertex of depth_out (the same device function), zeros where !(depth_out > 0);
+ *          with radius 0 it is ofx_backproject_depth's output bit for bit wherever the depth is > 0
+ *   normal_image = ofx_associate's n_q of point_image at the pixel (the same device function): zeros where its codes 3 or 4
+ *          apply (a hole, the image border, a 4-neighbour hole, a neighbour's z more than edge_max from the centre's, a zero
+ *          or non-finite cross product), else the normalised cross product, flipped to face the camera
+ * depth_out f32[H*W]; point_image f32[3*H*W] planar; normal_image f32[3*H*W] planar, may be NULL. Every output element is
+ * written on every call; the input is only read and must not overlap an output. height / width must be >= 1 and equal cam's.
+ * Stream-ordered: no handle, no allocation and no host sync inside the call (two launches, one without normal_image). */
+typedef struct ofx_prepare_params {
+  int32_t radius;      /* 0 .. OFX_PREPARE_RMAX: window (2r+1)^2; 0 = no filtering */
+  float sigma_s;       /* pixels, > 0 */
+  float sigma_r;       /* metres, > 0 */
+  float range_cut;     /* metres, > 0: a neighbour farther than this in depth from the centre is skipped */
+  float edge_max;      /* normal map: ofx_associate's edge_max, same meaning */
+  float normalizer;    /* u16 input: depth = u16 / normalizer */
+} ofx_prepare_params;
+#define OFX_PREPARE_RMAX 4
+int ofx_prepare_depth(const void* depth, int32_t is_u16, int32_t height, int32_t width, const ofx_camera* cam,
+                      const ofx_prepare_params* prm, float* depth_out, float* point_image, float* normal_image,
+                      ofx_stream_t s);
 
 /* ---------------- Skinned surface points of the TSDF (new capability; the reference has none — parity unpinned) ----------------
  * The tracking model read off the volume itself: canonical surface points, their outward normals and their anchors and

@@ -43,6 +43,14 @@ class SplatParams(ctypes.Structure):
 SPLAT_RMAX = 4   # OFX_SPLAT_RMAX (include/ofx.h)
 
 
+class PrepareParams(ctypes.Structure):
+    _fields_ = [("radius", c_int32), ("sigma_s", c_float), ("sigma_r", c_float), ("range_cut", c_float),
+                ("edge_max", c_float), ("normalizer", c_float)]
+
+
+PREPARE_RMAX = 4   # OFX_PREPARE_RMAX (include/ofx.h)
+
+
 class GnParams(ctypes.Structure):
     _fields_ = [("num_iter", c_int32), ("use_edge_weighting", c_int32), ("pcg_max_iter", c_int32), ("pcg_warm", c_int32),
                 ("lambda_flow", c_double), ("lambda_depth", c_double), ("lambda_arap", c_double),
@@ -95,6 +103,7 @@ _SIGS = {
     "ofx_mesh_emit": [P, P, P, P, P, P, P],
     "ofx_mesh_finish": [P, P, P, c_int64, P, P, P],
     "ofx_backproject_depth": [P, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float, c_float, P, P],
+    "ofx_prepare_depth": [P, c_int32, c_int32, c_int32, P, P, P, P, P, P],
     "ofx_depth_mesh_create": [P],
     "ofx_depth_mesh_destroy": [P],
     "ofx_depth_mesh_count": [P, P, c_int32, c_int32, c_float, P, P, P],

@@ -261,7 +261,8 @@ def fold_rigid(nodes, rot, trans, pose):
 
 def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
               valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3,
-              rigid_iters=0, rigid=None, occlusion=False, renderer=None, splat_radius=None, occl_margin=0.01, **assoc):
+              rigid_iters=0, rigid=None, occlusion=False, renderer=None, splat_radius=None, occl_margin=0.01,
+              depth_filter=None, **assoc):
     """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
     associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
     matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
@@ -280,8 +281,14 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     that stage, so a point that another part of the model hides is not matched to the surface in front of it. The mask
     stays on the device (no added host synchronisation), and the iteration's packed node tensor is built once for the
     render and the association. The result then gains "render": the last render's dict. occlusion=False is the loop
-    as it was."""
-    from .image_proc import backproject_depth_device
+    as it was.
+
+    depth_filter: None — the vertex map is backproject_depth_device of the raw depth, the loop as it was; True — the
+    frame is prepared first (image_proc.prepare_depth_device with its defaults: the bilateral-filtered depth's vertex
+    map); a dict overrides radius / sigma_s / sigma_r / range_cut (another key is a TypeError). The prepared vertex map
+    is what the rigid stage and every association read and what is returned as the third value; the association's own
+    edge_max keeps governing the gate, and the z-buffer stage does not read the frame."""
+    from .image_proc import PREPARE_DEFAULTS, backproject_depth_device, prepare_depth_device
     rigid_iters = int(rigid_iters)
     if rigid_iters < 0:
         raise ValueError("rigid_iters must not be negative")
@@ -291,6 +298,14 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         raise ValueError("rigid_iters > 0 needs a RigidAligner (rigid=...)")
     if occlusion and (renderer is None or splat_radius is None):
         raise ValueError("occlusion=True needs a ModelRenderer (renderer=...) and a splat_radius")
+    filt = None
+    if depth_filter is not None and depth_filter is not False:
+        filt = dict(PREPARE_DEFAULTS)
+        if depth_filter is not True:
+            unknown = set(depth_filter) - set(filt)
+            if unknown:
+                raise TypeError(f"unknown depth_filter parameters {sorted(unknown)}")
+            filt.update(depth_filter)
     d = solver.device
     prm = dict(ASSOC_DEFAULTS)
     unknown = set(assoc) - set(prm)
@@ -301,7 +316,11 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         prm["max_matches"] = solver.max_matches
     fx, fy, cx, cy = (float(v) for v in intr[:4])
     dep = depth if isinstance(depth, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(depth, np.float32))
-    vm = backproject_depth_device(dep.to(device=d, dtype=torch.float32), fx, fy, cx, cy)
+    dep = dep.to(device=d, dtype=torch.float32)
+    if filt is None:
+        vm = backproject_depth_device(dep, fx, fy, cx, cy)
+    else:
+        vm = prepare_depth_device(dep, fx, fy, cx, cy, normals=False, **filt)["point_image"]
     tloc, tconf = complete_node_motion_data if complete_node_motion_data is not None else (None, None)
     rot, trans, out, log = prev_rot, prev_trans, None, []
     rig = None

@@ -17,10 +17,9 @@
 // sqrt(dx²+(dy²+dz²)) <= max distance (Eigen's order).
 #include "ofx_common.h"
 #include "scan_flags.h"
+#include "warp_device.h"
 
 namespace ofx {
-
-__device__ __forceinline__ float fdiv(float a, float b) { return (float)((double)a / (double)b); }
 
 template <bool U16>
 __global__ __launch_bounds__(256) void k_backproject(const void* __restrict__ depth, int H, int W, float fx, float fy,
@@ -28,13 +27,13 @@ __global__ __launch_bounds__(256) void k_backproject(const void* __restrict__ de
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (p >= (int64_t)H * W) return;
   const int y = (int)(p / W), x = (int)(p % W);
-  float d;
-  if (U16) d = fdiv((float)((const uint16_t*)depth)[p], normalizer);
-  else d = ((const float*)depth)[p];
+  const float d = depth_px<U16>(depth, p, normalizer);
   if (d > 0.f) {
     const int64_t hw = (int64_t)H * W;
-    out[p] = fdiv(d * ((float)x - cx), fx);
-    out[hw + p] = fdiv(d * ((float)y - cy), fy);
+    float X, Y;
+    backproject_px(d, x, y, fx, fy, cx, cy, X, Y);
+    out[p] = X;
+    out[hw + p] = Y;
     out[2 * hw + p] = d;
   }
 }

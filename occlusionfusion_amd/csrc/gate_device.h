@@ -1,7 +1,8 @@
 // The skinned-point gate that assoc.hip, rigid.hip and splat.hip share: trip 1 (the load of a skinned point), trip 2 (its
 // ED warp) and the projective gate against a vertex map, plus the host checks and the <VALID, NRM> dispatch of the three
 // entry points. One definition, so that a point gated by any of the three kernels takes the same steps to the same bits;
-// the kernels' file headers say what each does with the result.
+// the kernels' file headers say what each does with the result. The gate's target normal (vertex_normal) is also what
+// prepare.hip writes as a frame's normal map.
 #pragma once
 #include <type_traits>
 
@@ -60,6 +61,30 @@ struct GateHit {
   float ex, ey, ez;   // q - point
 };
 
+// The target normal n_q of a vertex-map pixel from its vertex q and its left / right / upper / lower neighbours, all five
+// already in registers (border: the pixel lies on the image border): code 3 (hole) or 4 (no normal), or 0 with the unit
+// normal, facing the camera, in (nx, ny, nz). proj_gate's steps, and the normal map of prepare.hip.
+__device__ __forceinline__ int vertex_normal(bool border, float qx, float qy, float qz, float lx, float ly, float lz,
+                                             float rx, float ry, float rz, float ux, float uy, float uz, float dx,
+                                             float dy, float dz, float edge_max, float& nx, float& ny, float& nz) {
+  if (!(qz > 0.f)) return 3;
+  if (border || !(lz > 0.f && rz > 0.f && uz > 0.f && dz > 0.f) || fabsf(lz - qz) > edge_max ||
+      fabsf(rz - qz) > edge_max || fabsf(uz - qz) > edge_max || fabsf(dz - qz) > edge_max)
+    return 4;
+  const float ax = rx - lx, ay = ry - ly, az = rz - lz;
+  const float bx = dx - ux, by = dy - uy, bz = dz - uz;
+  float cx = ay * bz - az * by;
+  float cy = az * bx - ax * bz;
+  float cz = ax * by - ay * bx;
+  const float l2 = (cx * cx + cy * cy) + cz * cz;
+  if (!(l2 > 0.f && isfinite(l2))) return 4;
+  const float len = (float)sqrt((double)l2);
+  cx = cdiv(cx, len); cy = cdiv(cy, len); cz = cdiv(cz, len);
+  if (dot3(cx, cy, cz, qx, qy, qz) > 0.f) { cx = -cx; cy = -cy; cz = -cz; }
+  nx = cx; ny = cy; nz = cz;
+  return 0;
+}
+
 // The projective gate of the camera-space point and normal in s against the vertex map vmap (3 planes of c.H x c.W):
 // the first code of 2..6 that applies (assoc.hip's header), or 0 with the hit filled in. Trip 3: the five vertex-map
 // pixels; neighbour coordinates are clamped into the image, so the fifteen loads are unconditional and issue together.
@@ -81,20 +106,10 @@ __device__ __forceinline__ int proj_gate(const CamD& c, const float* __restrict_
   asm volatile("" :: "v"(qx), "v"(qy), "v"(qz), "v"(lx), "v"(ly), "v"(lz), "v"(rx), "v"(ry), "v"(rz), "v"(ux),
                "v"(uy), "v"(uz), "v"(dx), "v"(dy), "v"(dz));
   const bool border = u == 0 || v == 0 || u == c.W - 1 || v == c.H - 1;
-  if (!(qz > 0.f)) return 3;
-  if (border || !(lz > 0.f && rz > 0.f && uz > 0.f && dz > 0.f) || fabsf(lz - qz) > edge_max ||
-      fabsf(rz - qz) > edge_max || fabsf(uz - qz) > edge_max || fabsf(dz - qz) > edge_max)
-    return 4;
-  const float ax = rx - lx, ay = ry - ly, az = rz - lz;
-  const float bx = dx - ux, by = dy - uy, bz = dz - uz;
-  float cx = ay * bz - az * by;
-  float cy = az * bx - ax * bz;
-  float cz = ax * by - ay * bx;
-  const float l2 = (cx * cx + cy * cy) + cz * cz;
-  if (!(l2 > 0.f && isfinite(l2))) return 4;
-  const float len = (float)sqrt((double)l2);
-  cx = cdiv(cx, len); cy = cdiv(cy, len); cz = cdiv(cz, len);
-  if (dot3(cx, cy, cz, qx, qy, qz) > 0.f) { cx = -cx; cy = -cy; cz = -cz; }
+  float cx, cy, cz;
+  if (const int cd = vertex_normal(border, qx, qy, qz, lx, ly, lz, rx, ry, rz, ux, uy, uz, dx, dy, dz, edge_max, cx, cy,
+                                   cz))
+    return cd;
   const float ex = qx - s.x, ey = qy - s.y, ez = qz - s.z;
   const float d2 = (ex * ex + ey * ey) + ez * ez;
   if (d2 > dist_max * dist_max) return 5;

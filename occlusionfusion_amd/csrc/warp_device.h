@@ -52,6 +52,21 @@ __device__ __forceinline__ void ed_warp(const float4* __restrict__ nodes, const 
 
 __device__ __forceinline__ float cdiv(float a, float b) { return (float)((double)a / (double)b); }
 
+// Pixel p of a depth image in metres: f32 as it is, or u16 divided by the normalizer (correctly rounded)
+template <bool U16>
+__device__ __forceinline__ float depth_px(const void* __restrict__ depth, int64_t p, float normalizer) {
+  if (U16) return cdiv((float)((const uint16_t*)depth)[p], normalizer);
+  return ((const float*)depth)[p];
+}
+
+// The vertex of pixel (x, y) at depth d (image_proc.cpp:351-401): f32 d·(x − cx), the quotient by fx correctly rounded;
+// z = d. One definition for ofx_backproject_depth and ofx_prepare_depth.
+__device__ __forceinline__ void backproject_px(float d, int x, int y, float fx, float fy, float cx, float cy, float& X,
+                                               float& Y) {
+  X = cdiv(d * ((float)x - cx), fx);
+  Y = cdiv(d * ((float)y - cy), fy);
+}
+
 // WarpField.deform_normals: deform_lbs with zero translation, weights==0 skipped (warpfield.py:208-231,312-345);
 // the blend, not yet normalised
 __device__ __forceinline__ void ed_warp_normal(const float4* __restrict__ nodes, const int ids[4], const float w[4],

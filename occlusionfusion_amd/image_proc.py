@@ -8,6 +8,8 @@
                                                                                      -> ofx_depth_mesh_*
   depth_2_pc / target cloud  NonRigidICP/model/geometry.py:44-59 + Registration.optimize's masked cloud and
                              map_pixel_to_pcd (registration_fusion.py:104-109,388-395) -> ofx_depth_to_pc
+  prepare_depth_device       (no reference twin) bilateral-filtered depth, its vertex map and its normal map: what
+                             the depth tracker reads a frame through (tests/prepare_ref.py)      -> ofx_prepare_depth
 
 Results are bit-identical to the reference C++ (backproject, mesh) and to the numpy float64 expression
 rounded to f32 (depth_2_pc): tests/test_gpu_frontend.py. There is no CPU fallback.
@@ -50,6 +52,31 @@ def backproject_depth_device(depth, fx, fy, cx, cy, normalizer=1000.0, out=None)
     call("ofx_backproject_depth", ptr(d), 1 if is_u16 else 0, H, W, float(fx), float(fy), float(cx), float(cy),
          float(normalizer), ptr(out), stream_ptr())
     return out
+
+
+PREPARE_DEFAULTS = dict(radius=3, sigma_s=2.0, sigma_r=0.01, range_cut=None)
+
+
+def prepare_depth_device(depth, fx, fy, cx, cy, radius=3, sigma_s=2.0, sigma_r=0.01, range_cut=None, edge_max=0.03,
+                         normals=True, normalizer=1000.0):
+    """A depth frame as the tracker should read it (torch.ops.ofx.prepare_depth -> ofx_prepare_depth; no reference
+    twin): depth (H, W) float32 metres or uint16/int16 (scaled by 1/normalizer) device tensor, never written ->
+    dict(depth (H,W) f32: the bilateral-filtered depth — window (2·radius+1)², spatial sigma sigma_s in pixels, range
+    sigma sigma_r in metres, neighbours farther than range_cut metres in depth from the centre skipped (None: 3·sigma_r),
+    holes stay holes and nothing bleeds across a depth edge; point_image (3,H,W): its vertex map, as
+    backproject_depth_device writes one; normals (3,H,W): the association gate's target normal of that vertex map at
+    every pixel under edge_max, zeros where it has none — None with normals=False). radius 0 filters nothing. Enqueued on
+    torch's current stream; nothing is read back. The integrate keeps reading the raw frame."""
+    assert depth.dim() == 2, "depth image must be (H, W)"
+    if depth.dtype != torch.float32:
+        assert depth.dtype in (torch.uint16, torch.int16), "integer depth must be 16-bit (uint16 mm)"
+    if range_cut is None:
+        range_cut = 3.0 * float(sigma_r)
+    from . import ops  # noqa: F401  (registers torch.ops.ofx.*)
+    d, p, n = torch.ops.ofx.prepare_depth(depth, [float(fx), float(fy), float(cx), float(cy)], int(radius),
+                                          float(sigma_s), float(sigma_r), float(range_cut), float(edge_max),
+                                          float(normalizer), bool(normals))
+    return {"depth": d, "point_image": p, "normals": n if normals else None}
 
 
 def backproject_depth(depth_image, fx, fy, cx, cy, normalizer=1000.0, device=None):

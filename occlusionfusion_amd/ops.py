@@ -308,6 +308,41 @@ def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, int
             points.new_empty((P if normals is not None else 0, 3), dtype=f))
 
 
+# --------------------------------------------------------------------------------------------- depth preparation
+@_op("prepare_depth", mutates_args=())
+def prepare_depth(depth: Tensor, intr: List[float], radius: int, sigma_s: float, sigma_r: float, range_cut: float,
+                  edge_max: float, normalizer: float, with_normals: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """ofx_prepare_depth (new capability, no reference twin): the bilateral-filtered depth of a frame, its vertex map and
+    its normal map. depth (H,W): f32 metres or 16-bit integers (read as uint16, scaled by 1/normalizer); never written.
+    -> depth f32 (H,W), point_image f32 (3,H,W), normals f32 (3,H,W) — the gate's target normal of point_image at every
+    pixel under edge_max, zeros where it has none; with_normals=False skips the normal map and returns an empty (0,H,W)
+    tensor in its place. radius 0..4 (0: no filtering), sigma_s in pixels, sigma_r and range_cut in metres."""
+    if depth.dim() != 2:
+        raise ValueError(f"prepare_depth: depth must be (H, W), got {tuple(depth.shape)}")
+    is_u16 = depth.dtype != torch.float32
+    if is_u16 and depth.dtype not in (torch.uint16, torch.int16):
+        raise ValueError(f"prepare_depth: depth must be float32 or 16-bit integer, got {depth.dtype}")
+    H, W = depth.shape
+    d = depth.contiguous()
+    cam = _camera(intr, H, W)
+    prm = _lib.PrepareParams(int(radius), float(sigma_s), float(sigma_r), float(range_cut), float(edge_max),
+                             float(normalizer))
+    out = torch.empty((H, W), dtype=torch.float32, device=d.device)
+    pimg = torch.empty((3, H, W), dtype=torch.float32, device=d.device)
+    nimg = torch.empty((3 if with_normals else 0, H, W), dtype=torch.float32, device=d.device)
+    call("ofx_prepare_depth", ptr(d), 1 if is_u16 else 0, H, W, byref(cam), byref(prm), ptr(out), ptr(pimg),
+         ptr(nimg) if with_normals else None, _stream(d))
+    return out, pimg, nimg
+
+
+@prepare_depth.register_fake
+def _(depth, intr, radius, sigma_s, sigma_r, range_cut, edge_max, normalizer, with_normals):
+    H, W = depth.shape
+    f = torch.float32
+    return (depth.new_empty((H, W), dtype=f), depth.new_empty((3, H, W), dtype=f),
+            depth.new_empty((3 if with_normals else 0, H, W), dtype=f))
+
+
 # --------------------------------------------------------------------------------------------- surface points
 @_op("surface_points", mutates_args=("state", "points", "normals", "anchors_out", "weights_out", "voxel", "valid", "code",
                                      "count"))
@@ -536,4 +571,4 @@ def _(state, handle, n_nodes, num_iter):
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
-       "rigid_icp", "splat_points")
+       "rigid_icp", "splat_points", "prepare_depth")

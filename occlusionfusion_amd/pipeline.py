@@ -181,7 +181,7 @@ class FusionPipeline:
         return dict(occlusion=True, renderer=self._renderer, splat_radius=splat_radius, occl_margin=occl_margin)
 
     def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
-                      occ=(False, None, 0.01)):
+                      occ=(False, None, 0.01), depth_filter=None):
         from .association import ProjectiveAssociator, icp_track
         M = int(max_model_points)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
@@ -199,7 +199,7 @@ class FusionPipeline:
                                 m["normals"], m["anchors"], m["weights"], m["valid"], fi.im[-1], self.intr,
                                 self.prev_rot, self.prev_trans, (fi.tpos, fi.conf) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M),
-                                **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
+                                depth_filter=depth_filter, **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out
@@ -217,7 +217,7 @@ class FusionPipeline:
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
                    max_model_points=65536, w_min=1.0, rigid_iters=0, occlusion=False, splat_radius=None,
-                   occl_margin=0.01, **assoc):
+                   occl_margin=0.01, depth_filter=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -242,10 +242,14 @@ class FusionPipeline:
         (association.ModelRenderer, owned by the pipeline): points that the model itself hides under the current
         estimate, by more than occl_margin metres, are left out of that stage. splat_radius defaults to the volume's
         voxel size for the volume model (it carries normals) and to half of it for the canonical points (they do not).
-        The result then carries "render": the last render's dict of device tensors. No host read is added."""
+        The result then carries "render": the last render's dict of device tensors. No host read is added.
+
+        depth_filter (both models; None / True / a dict of radius, sigma_s, sigma_r, range_cut): the tracker reads the
+        bilateral-filtered frame's vertex map (image_proc.prepare_depth_device) instead of the raw one's; the staged
+        and integrated frame stays the raw one, so the fused volume does not change with the filter itself."""
         if model == "volume":
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
-                                      assoc, (occlusion, splat_radius, occl_margin))
+                                      assoc, (occlusion, splat_radius, occl_margin), depth_filter)
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
@@ -260,6 +264,7 @@ class FusionPipeline:
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
                                 (fi.tpos, fi.conf) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
+                                depth_filter=depth_filter,
                                 **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),
                                 **assoc)
         out["assoc"] = log

@@ -503,7 +503,7 @@ class Registration:
         return res
 
     def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
-              rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, **assoc):
+              rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, depth_filter=None, **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -523,7 +523,10 @@ class Registration:
         (association.ModelRenderer, ofx_splat_points, owned by this object) and the points the model itself hides —
         more than occl_margin metres behind its z-buffer — are left out of that stage; splat_radius (metres) defaults
         to the volume's voxel size when the model carries normals and to half of it when it does not. The result then
-        has "render": the last render's dict of device tensors. No host synchronisation is added."""
+        has "render": the last render's dict of device tensors. No host synchronisation is added.
+        depth_filter (None / True / a dict of radius, sigma_s, sigma_r, range_cut): the rigid stage and the associations
+        read the bilateral-filtered frame's vertex map (image_proc.prepare_depth_device) instead of the raw one's; tgt_pcd
+        / pix_2_pcd are still the raw depth's. None is the loop as it was."""
         from .association import ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track
         depth = torch.as_tensor(np.ascontiguousarray(target_frame_data["im"][-1], np.float32), device=self.device)
         self.tgt_pcd, self.pix_2_pcd = depth_2_pc_device(depth, self.intrinsics)
@@ -553,7 +556,8 @@ class Registration:
         out, log, _ = icp_track(self._assoc, self.solver, self.graph.nodes, self.graph.edges, self.graph.edges_weights,
                                 self.source_pcd, nrm, self.point_anchors, self.anchor_weight, None, depth,
                                 self._intr4(), self.prev_rot, self.prev_trans, complete_node_motion_data, icp_iters,
-                                rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None), **occ, **assoc)
+                                rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None),
+                                depth_filter=depth_filter, **occ, **assoc)
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)
