@@ -43,6 +43,10 @@
  *   ofx_surface_*           (new) skinned surface points of the TSDF, the tracking model — (no reference twin: the
  *                           reference re-meshes and re-skins per frame, tsdf.get_deformed_model / optimizer.update in
  *                           fusion_tests/lepard_nicp_test.py:471,537. Parity unpinned; restated by tests/surface_ref.py)
+ *   ofx_grow_*              (new) graph nodes added where the sampled model leaves the graph's coverage, with blended
+ *                           transforms and edge rows — EDGraph.update behind WarpField.find_unreachable_nodes,
+ *                           embedded_deformation_graph.py:496-609, warpfield.py:462-485 (its greedy `<` loop and 2·coverage
+ *                           kept; transforms and edges have no twin. Restated op for op by tests/grow_ref.py)
  *   ofx_splat_*             (new) z-buffer of the warped model points in the live frame and the occlusion code of every
  *                           point — (no reference twin: the reference renders the live model from a warped marching-
  *                           cubes mesh, tsdf.get_deformed_model and NonRigidICP/model/point_render.py. Parity unpinned;
@@ -152,6 +156,26 @@ int ofx_skin_volume(const ofx_volume_desc* desc, const float* nodes, int32_t n_n
 #define OFX_PALETTE 64
 int ofx_skin_palette(const uint16_t* anchors, int32_t n_list, int32_t k, int32_t n_nodes, uint16_t* pal_ids,
                      int32_t* pal_n, uint8_t* local_anchors, ofx_stream_t s);
+/* In-place update of the skin cache after nodes were appended (ofx_grow_nodes): nodes f32[(n_old + *n_added)*3], n_added a
+ * DEVICE int32 (count[1] of ofx_grow_nodes: no host read between the two calls). A voxel's skin can change only if a new
+ * node lies within the 4-sigma cut-off of it: a new node farther away that enters its top-K replaces an anchor that was
+ * already past the cut-off, and both are written as 0xFFFF with weight 0. So only bricks whose AABB lies within the cull
+ * radius of a new node (ofx_skin_volume_bricks' test) need work.
+ * ofx_skin_grow_plan: one thread per brick -> the work list, work_bricks / work_slots int32[num_bricks] each: first the
+ *   touched bricks of brick_list (ascending brick id) at their existing slots, then the touched unlisted bricks that now
+ *   have >= K of all nodes within the cull radius (ascending id: what a full ofx_skin_volume_bricks would add) at slots
+ *   n_list, n_list + 1, ...; counts (DEVICE int32[2]) = [re-skinned, appended].
+ * ofx_skin_grow_apply: ofx_skin_volume and ofx_skin_palette (the same kernels, a slot indirection) over the first n_work =
+ *   re-skinned + appended work entries against all n_nodes nodes; anchors / weights / pal_ids / pal_n / local_anchors are
+ *   the cache's arrays enlarged by the caller to n_list + appended slots. The caller appends work_bricks[re-skinned ..
+ *   n_work) to its brick list, which is then no longer ascending (ofx_surface_points and ofx_integrate* take any order).
+ *   The result equals a full rebuild on the grown node set, slot for brick, bit for bit. */
+int ofx_skin_grow_plan(const ofx_volume_desc* desc, const float* nodes, int32_t n_old, const int32_t* n_added,
+                       double node_coverage, int32_t k, const int32_t* brick_list, int32_t n_list, int32_t* work_bricks,
+                       int32_t* work_slots, int32_t* counts, ofx_stream_t s);
+int ofx_skin_grow_apply(const ofx_volume_desc* desc, const float* nodes, int32_t n_nodes, double node_coverage, int32_t k,
+                        const int32_t* work_bricks, const int32_t* work_slots, int32_t n_work, uint16_t* anchors,
+                        float* weights, uint16_t* pal_ids, int32_t* pal_n, uint8_t* local_anchors, ofx_stream_t s);
 /* Skinning of arbitrary points: anchors int32[P*K] (-1 beyond 4σ), weights f32[P*K], valid u8[P] */
 int ofx_skin_points(const float* points, int64_t n_points, const float* nodes, int32_t n_nodes,
                     double node_coverage, int32_t k, int32_t* anchors, float* weights, uint8_t* valid,
@@ -520,6 +544,52 @@ int ofx_surface_points(void* handle, const ofx_volume_desc* desc, const float* t
                        const float* skin_weights, int32_t k, float w_min, int32_t max_points, float* points,
                        float* normals, int32_t* anchors, float* weights, int32_t* voxel, uint8_t* valid, uint8_t* code,
                        int32_t* count, ofx_stream_t s);
+
+/* ---------------- Growing the graph from the sampled model (new capability — parity unpinned) ----------------
+ * New nodes at model points that no node supports, a spacing apart, with transforms blended from the point's anchors and
+ * an edge row each: DynamicFusion's graph update on the rows ofx_surface_points writes. The reference's twin is the host
+ * loop of EDGraph.update behind WarpField.find_unreachable_nodes (embedded_deformation_graph.py:496-609, warpfield.py:
+ * 462-485), which re-meshes, re-derives geodesic edges and solves ARAP for the transforms. Restated op for op by
+ * tests/grow_ref.py. f32, no contraction, every step fixed.
+ * Inputs: the padded model rows points f32[M,3], anchors i32[M,4], weights f32[M,4] (both 16-byte aligned), valid u8[M],
+ * M = n_points; nodes f32[(n_nodes + max_new),3], R f32[.,9] row-major and T f32[.,3] (node-relative, as ofx_pack_nodes
+ * takes them), edges i32[.,k_e] and edge_weights f32[.,k_e] with the same number of rows: rows [0, n_nodes) are read,
+ * rows [n_nodes, n_nodes + selected) are written, nothing else is touched.
+ * Candidate: row r with valid[r] != 0, its four anchors in [0, n_nodes), a finite point, and dist_min(r) > min_dist
+ *   (a NaN fails), dist_min = f32(sqrt(f64(d2))), d2 = min over all nodes of (dx^2 + dy^2) + dz^2 (the ofx_knn_points form;
+ *   NaN distances are skipped as fminf does).
+ * Selection: the candidates in ascending row order; candidate r is selected iff no EARLIER SELECTED candidate s has
+ *   f32(sqrt(f64(d2(r, s)))) < spacing (strict, as the reference's loop), until max_new are selected: the sequential
+ *   greedy loop's result. The cap flag is 1 iff a candidate that the loop would have selected next was left out.
+ * New node j = n_nodes + rank of the selected row, p its point, a_k / w_k its anchors and weights:
+ *   nodes[j] = p
+ *   T[j]     = x' - p, x' = ofx_deform_points (normals = 0, k = 4) of p under (R, T, nodes), bit for bit
+ *   R[j]     : in f64. q_k = unit quaternion (w, x, y, z) of R[a_k] by Shepperd's form — with tr = (m00 + m11) + m22, the
+ *              branch of the largest of (tr, m00, m11, m22), the first of equals: s = 2*sqrt(tr + 1), w = s/4,
+ *              x = (m21 - m12)/s, y = (m02 - m20)/s, z = (m10 - m01)/s; or s = 2*sqrt(((1 + m00) - m11) - m22), x = s/4,
+ *              w = (m21 - m12)/s, y = (m01 + m10)/s, z = (m02 + m20)/s; and cyclically — divided by its norm
+ *              sqrt(((w^2 + x^2) + y^2) + z^2) (identity if that is not positive and finite); q_k negated if its dot
+ *              product with q_0, ((w w' + x x') + y y') + z z', is < 0; acc = w_0*q_0, then acc += w_k*q_k for k = 1..3;
+ *              q = acc / norm(acc) (identity if not positive and finite);
+ *              R = [1 - 2(yy + zz), 2(xy - zw), 2(xz + yw); 2(xy + zw), 1 - 2(xx + zz), 2(yz - xw); 2(xz - yw), 2(yz + xw),
+ *              1 - 2(xx + yy)], each entry rounded to f32. No libm call but sqrt.
+ *   edges[j] : the k_e nearest OTHER nodes among all n_nodes + selected, ascending by (d2, id), -1 past the node count;
+ *   edge_weights[j] : w_i = f32(exp(f64(-(d*d) / (2c^2)))) with d = f32(sqrt(f64(d2))), the quotient correctly rounded and
+ *              2c^2 = (2*node_coverage)*node_coverage in f32; divided by their f32 sum in order (by their number if the
+ *              sum is 0), 0 where the edge is -1 (ofx_edges_geodesic's weights with Euclidean distances). Rows of old
+ *              nodes are not rewritten: the ARAP block of an edge (i, j) couples both nodes in J^T J anyway.
+ * count (DEVICE int32[3]) = [candidates, selected, cap flag]. n_points == 0 or max_new == 0 is legal: count = [0, 0, 0],
+ * nothing else happens (the other buffers are not looked at then, and may be NULL). Refused: null buffers, k_e outside [1, 8], n_points or max_new above the handle's, n_nodes < 1,
+ * spacing or node_coverage not positive and finite, NaN min_dist (OFX_ERR_ARG); n_nodes + max_new > 65534, and at create
+ * max_points > 65536 or max_new > 4096 (OFX_ERR_RANGE: the selected positions live in LDS). Stream-ordered: no
+ * allocation and no host sync inside the call; the handle owns the flags, ranks and row lists. Order comes from a scan and
+ * a single-workgroup loop, never from atomics: two calls give the same bytes. */
+int ofx_grow_create(int32_t max_points, int32_t max_new, void** handle);
+int ofx_grow_destroy(void* handle);
+int ofx_grow_nodes(void* handle, const float* points, const int32_t* anchors, const float* weights,
+                   const uint8_t* valid, int32_t n_points, float* nodes, int32_t n_nodes, float* R, float* T,
+                   int32_t* edges, float* edge_weights, int32_t k_e, float node_coverage, float min_dist, float spacing,
+                   int32_t max_new, int32_t* count, ofx_stream_t s);
 
 /* ---------------- Standalone skinning / anchors ---------------- */
 /* csrc twins, exact (Eigen summation order, list tie order, f32 weights): outputs (H, W, 4) images,

@@ -81,6 +81,8 @@ _SIGS = {
     "ofx_skin_volume_bricks": [P, P, c_int32, c_double, c_int32, P, P, P],
     "ofx_skin_volume": [P, P, c_int32, c_double, c_int32, P, c_int32, P, P, P],
     "ofx_skin_palette": [P, c_int32, c_int32, c_int32, P, P, P, P],
+    "ofx_skin_grow_plan": [P, P, c_int32, P, c_double, c_int32, P, c_int32, P, P, P, P],
+    "ofx_skin_grow_apply": [P, P, c_int32, c_double, c_int32, P, P, c_int32, P, P, P, P, P, P],
     "ofx_skin_points": [P, c_int64, P, c_int32, c_double, c_int32, P, P, P, P],
     "ofx_skin_volume_to_dense": [P, P, c_int32, P, P, c_int32, P, P, P, P],
     "ofx_pack_nodes": [P, P, P, c_int32, P, P],
@@ -121,6 +123,9 @@ _SIGS = {
     "ofx_surface_create": [c_int32, P],
     "ofx_surface_destroy": [P],
     "ofx_surface_points": [P, P, P, P, P, c_int32, P, P, c_int32, c_float, c_int32, P, P, P, P, P, P, P, P, P],
+    "ofx_grow_create": [c_int32, c_int32, P],
+    "ofx_grow_destroy": [P],
+    "ofx_grow_nodes": [P, P, P, P, P, c_int32, P, c_int32, P, P, P, P, c_int32, c_float, c_float, c_float, c_int32, P, P],
     "ofx_pixel_anchors_euclidean": [P, c_int32, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_pixel_anchors_geodesic": [P, P, c_int32, c_int64, P, c_int32, c_int32, c_float, P, P, P],
     "ofx_remap_anchors": [P, c_int64, P, c_int32, P, P],

@@ -117,8 +117,10 @@ __global__ __launch_bounds__(256) void k_brick_cull(BrickGeom g, const float* __
 }
 
 // ---- single-workgroup ordered compaction of a flag array into an index list ----
+// (base, nullable: a device offset of the first written entry — the list continues one written before)
 __global__ __launch_bounds__(1024) void k_compact(const uint8_t* __restrict__ flags, int64_t n,
-                                                   int32_t* __restrict__ list, int32_t* __restrict__ count) {
+                                                   int32_t* __restrict__ list, int32_t* __restrict__ count,
+                                                   const int32_t* __restrict__ base) {
   __shared__ int64_t part[1024];
   int64_t per = (n + blockDim.x - 1) / blockDim.x;
   int64_t s = threadIdx.x * per, e = min(n, s + per);
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(1024) void k_compact(const uint8_t* __restrict__ fl
     *count = (int32_t)acc;
   }
   __syncthreads();
-  int64_t o = part[threadIdx.x];
+  int64_t o = part[threadIdx.x] + (base ? *base : 0);
   for (int64_t i = s; i < e; ++i)
     if (flags[i]) list[o++] = (int32_t)i;
 }
@@ -140,12 +142,14 @@ __global__ __launch_bounds__(1024) void k_compact(const uint8_t* __restrict__ fl
 // ---- per-voxel k-NN for listed bricks ----
 __global__ __launch_bounds__(256) void k_skin_volume(BrickGeom g, const float* __restrict__ nodes, int n_nodes,
                                                       float cull_r2, float cutoff, float denom, int K,
-                                                      const int32_t* __restrict__ list, ushort4* __restrict__ anchors,
+                                                      const int32_t* __restrict__ list,
+                                                      const int32_t* __restrict__ slots, ushort4* __restrict__ anchors,
                                                       float4* __restrict__ weights) {
   __shared__ float4 sc[kTile];
   __shared__ int s_nc;
-  const int64_t slot = blockIdx.x;
-  const int64_t b = list[slot];
+  // slots (nullable): where entry blockIdx.x of the list keeps its skin (ofx_skin_grow_apply); else its list position
+  const int64_t slot = slots ? slots[blockIdx.x] : blockIdx.x;
+  const int64_t b = list[blockIdx.x];
   int64_t bz = b % g.nbz;
   int64_t r = b / g.nbz;
   int64_t by = r % g.nby;
@@ -213,12 +217,13 @@ __global__ __launch_bounds__(256) void k_skin_volume(BrickGeom g, const float* _
 // block scan of popcounts); each voxel's anchors re-expressed as palette ranks (uint8, kNoLocal for
 // skin-invalid voxels and unused slots). pal_n > kPal marks an overflowing brick (palette unused).
 __global__ __launch_bounds__(256) void k_skin_palette(const ushort4* __restrict__ anchors, int K, int n_nodes,
+                                                       const int32_t* __restrict__ slots,
                                                        uint16_t* __restrict__ pal_ids, int32_t* __restrict__ pal_n,
                                                        uchar4* __restrict__ local) {
   __shared__ uint32_t s_bits[2048];
   __shared__ int s_pre[2048 + 1];
   __shared__ int s_tsum[256];
-  const int64_t slot = blockIdx.x;
+  const int64_t slot = slots ? slots[blockIdx.x] : blockIdx.x;
   const int nw = (n_nodes + 31) >> 5;
   for (int i = threadIdx.x; i < nw; i += 256) s_bits[i] = 0u;
   __syncthreads();
@@ -359,6 +364,73 @@ __global__ void k_skin_to_dense(BrickGeom g, int32_t x_lo, int32_t x_n, const in
   }
 }
 
+// ---- in-place update of the skin cache after nodes [n_old, n_old + *n_added) were appended ----
+// One thread per brick. A brick is touched if a NEW node lies within the cull radius of its AABB (k_brick_cull's test):
+// only then can a voxel's skin change. flag_a: touched and listed; flag_b: touched, unlisted, and now >= K of ALL nodes
+// within the cull radius (what a full ofx_skin_volume_bricks would list).
+__global__ __launch_bounds__(256) void k_grow_plan(BrickGeom g, const float* __restrict__ nodes, int n_old,
+                                                    const int32_t* __restrict__ n_added, float cull_r2, int K,
+                                                    const int32_t* __restrict__ slot_of, uint8_t* __restrict__ flag_a,
+                                                    uint8_t* __restrict__ flag_b) {
+  __shared__ float4 sn[kTile];
+  const int n_new = n_old + *n_added;
+  int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  bool active = b < g.n_bricks;
+  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  if (active) {
+    int64_t bz = b % g.nbz;
+    int64_t r = b / g.nbz;
+    int64_t by = r % g.nby;
+    int64_t bx = r / g.nby + g.bx0;
+    int i0 = (int)bx * kBrick, j0 = (int)by * kBrick, k0 = (int)bz * kBrick;
+    int i1 = min(i0 + kBrick - 1, g.Dx - 1), j1 = min(j0 + kBrick - 1, g.Dy - 1), k1 = min(k0 + kBrick - 1, g.Dz - 1);
+    lo[0] = vox2world(g.ox, g.vs, i0); hi[0] = vox2world(g.ox, g.vs, i1);
+    lo[1] = vox2world(g.oy, g.vs, j0); hi[1] = vox2world(g.oy, g.vs, j1);
+    lo[2] = vox2world(g.oz, g.vs, k0); hi[2] = vox2world(g.oz, g.vs, k1);
+  }
+  bool touched = false;
+  int count = 0;
+  // pass 0: the new nodes (touched); pass 1: all nodes, counted by the touched unlisted bricks only
+  for (int pass = 0; pass < 2; ++pass) {
+    const int first = pass == 0 ? n_old : 0;
+    const bool mine = active && (pass == 0 || (touched && slot_of[b] < 0));
+    for (int t0 = first; t0 < n_new; t0 += kTile) {   // (bounds are workgroup-uniform)
+      int nt = min(kTile, n_new - t0);
+      __syncthreads();
+      for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+        const float* p = nodes + 3 * (int64_t)(t0 + i);
+        sn[i] = make_float4(p[0], p[1], p[2], 0.f);
+      }
+      __syncthreads();
+      if (mine && (pass == 0 ? !touched : count < K)) {
+        for (int i = 0; i < nt; ++i) {
+          float4 n = sn[i];
+          float ex = fmaxf(fmaxf(lo[0] - n.x, n.x - hi[0]), 0.f);
+          float ey = fmaxf(fmaxf(lo[1] - n.y, n.y - hi[1]), 0.f);
+          float ez = fmaxf(fmaxf(lo[2] - n.z, n.z - hi[2]), 0.f);
+          if (ex * ex + ey * ey + ez * ez <= cull_r2) { touched = true; ++count; }
+        }
+      }
+    }
+    if (pass == 0) count = 0;
+  }
+  if (active) {
+    const bool listed = slot_of[b] >= 0;
+    flag_a[b] = touched && listed ? 1 : 0;
+    flag_b[b] = touched && !listed && count >= K ? 1 : 0;
+  }
+}
+
+// work entry i -> its slot: the brick's own for the re-skinned ones, n_list_old + rank for the appended ones
+__global__ __launch_bounds__(256) void k_grow_slots(const int32_t* __restrict__ work, const int32_t* __restrict__ counts,
+                                                     const int32_t* __restrict__ slot_of, int n_list_old,
+                                                     int32_t* __restrict__ slots) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int na = counts[0], nb = counts[1];
+  if (i >= na + nb) return;
+  slots[i] = i < na ? slot_of[work[i]] : n_list_old + (i - na);
+}
+
 struct SkinConsts {
   float cutoff, denom, cull_r2;
 };
@@ -394,7 +466,8 @@ int ofx_skin_volume_bricks(const ofx_volume_desc* desc, const float* nodes, int3
   hipLaunchKernelGGL(k_brick_cull, dim3(grid_for(g.n_bricks, 256, 1 << 30)), dim3(256), 0, hs, g, nodes, n_nodes,
                      c.cull_r2, k, flags);
   OFX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, hs, flags, g.n_bricks, brick_list, count);
+  hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, hs, (const uint8_t*)flags, g.n_bricks, brick_list, count,
+                     (const int32_t*)nullptr);
   OFX_LAUNCH_CHECK();
   OFX_HIP(hipFreeAsync(flags, hs));
   return OFX_OK;
@@ -412,7 +485,7 @@ int ofx_skin_volume(const ofx_volume_desc* desc, const float* nodes, int32_t n_n
   OFX_CHECK_ARG(brick_list && anchors && weights, "null buffer");
   SkinConsts c = skin_consts(node_coverage);
   hipLaunchKernelGGL(k_skin_volume, dim3(n_list), dim3(256), 0, as_stream(s), g, nodes, n_nodes, c.cull_r2, c.cutoff,
-                     c.denom, k, brick_list, (ushort4*)anchors, (float4*)weights);
+                     c.denom, k, brick_list, (const int32_t*)nullptr, (ushort4*)anchors, (float4*)weights);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
@@ -424,6 +497,59 @@ int ofx_skin_palette(const uint16_t* anchors, int32_t n_list, int32_t k, int32_t
   if (n_list == 0) return OFX_OK;
   OFX_CHECK_ARG(anchors && pal_ids && pal_n && local_anchors, "null buffer");
   hipLaunchKernelGGL(k_skin_palette, dim3(n_list), dim3(256), 0, as_stream(s), (const ushort4*)anchors, k, n_nodes,
+                     (const int32_t*)nullptr, pal_ids, pal_n, (uchar4*)local_anchors);
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+int ofx_skin_grow_plan(const ofx_volume_desc* desc, const float* nodes, int32_t n_old, const int32_t* n_added,
+                       double node_coverage, int32_t k, const int32_t* brick_list, int32_t n_list, int32_t* work_bricks,
+                       int32_t* work_slots, int32_t* counts, ofx_stream_t s) {
+  BrickGeom g;
+  int st = make_geom(desc, &g);
+  if (st) return st;
+  OFX_CHECK_ARG(nodes && n_added && work_bricks && work_slots && counts, "null buffer");
+  OFX_CHECK_ARG(n_old > 0 && k >= 1 && k <= 4, "bad n_old/k");
+  OFX_CHECK_ARG(node_coverage > 0, "node_coverage must be > 0");
+  OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks && (n_list == 0 || brick_list), "bad brick list");
+  SkinConsts c = skin_consts(node_coverage);
+  hipStream_t hs = as_stream(s);
+  int32_t* slot_of = nullptr;
+  uint8_t* flags = nullptr;
+  OFX_HIP(hipMallocAsync((void**)&slot_of, g.n_bricks * sizeof(int32_t), hs));
+  OFX_HIP(hipMallocAsync((void**)&flags, 2 * g.n_bricks, hs));
+  OFX_HIP(hipMemsetAsync(slot_of, 0xFF, g.n_bricks * sizeof(int32_t), hs));
+  if (n_list > 0) hipLaunchKernelGGL(k_slot_map, dim3(grid_for(n_list, 256)), dim3(256), 0, hs, brick_list, n_list, slot_of);
+  hipLaunchKernelGGL(k_grow_plan, dim3(grid_for(g.n_bricks, 256, 1 << 30)), dim3(256), 0, hs, g, nodes, n_old, n_added,
+                     c.cull_r2, k, (const int32_t*)slot_of, flags, flags + g.n_bricks);
+  hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, hs, (const uint8_t*)flags, g.n_bricks, work_bricks, counts,
+                     (const int32_t*)nullptr);
+  hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, hs, (const uint8_t*)(flags + g.n_bricks), g.n_bricks, work_bricks,
+                     counts + 1, (const int32_t*)counts);
+  hipLaunchKernelGGL(k_grow_slots, dim3(grid_for(g.n_bricks, 256, 1 << 30)), dim3(256), 0, hs,
+                     (const int32_t*)work_bricks, (const int32_t*)counts, (const int32_t*)slot_of, n_list, work_slots);
+  OFX_LAUNCH_CHECK();
+  OFX_HIP(hipFreeAsync(flags, hs));
+  OFX_HIP(hipFreeAsync(slot_of, hs));
+  return OFX_OK;
+}
+
+int ofx_skin_grow_apply(const ofx_volume_desc* desc, const float* nodes, int32_t n_nodes, double node_coverage, int32_t k,
+                        const int32_t* work_bricks, const int32_t* work_slots, int32_t n_work, uint16_t* anchors,
+                        float* weights, uint16_t* pal_ids, int32_t* pal_n, uint8_t* local_anchors, ofx_stream_t s) {
+  BrickGeom g;
+  int st = make_geom(desc, &g);
+  if (st) return st;
+  OFX_CHECK_ARG(nodes && n_nodes > 0 && k >= 1 && k <= 4 && k <= n_nodes, "bad nodes/k");
+  if (n_nodes >= 0xFFFF) { set_error("n_nodes %d exceeds 65534 (uint16 anchors)", n_nodes); return OFX_ERR_RANGE; }
+  OFX_CHECK_ARG(n_work >= 0 && n_work <= g.n_bricks, "bad n_work");
+  if (n_work == 0) return OFX_OK;
+  OFX_CHECK_ARG(work_bricks && work_slots && anchors && weights && pal_ids && pal_n && local_anchors, "null buffer");
+  SkinConsts c = skin_consts(node_coverage);
+  hipStream_t hs = as_stream(s);
+  hipLaunchKernelGGL(k_skin_volume, dim3(n_work), dim3(256), 0, hs, g, nodes, n_nodes, c.cull_r2, c.cutoff, c.denom, k,
+                     work_bricks, work_slots, (ushort4*)anchors, (float4*)weights);
+  hipLaunchKernelGGL(k_skin_palette, dim3(n_work), dim3(256), 0, hs, (const ushort4*)anchors, k, n_nodes, work_slots,
                      pal_ids, pal_n, (uchar4*)local_anchors);
   OFX_LAUNCH_CHECK();
   return OFX_OK;

@@ -390,6 +390,43 @@ def surface_outputs(max_points, device, n_list=None):
             torch.empty(2, dtype=i, device=device))
 
 
+# --------------------------------------------------------------------------------------------- graph growth
+@_op("grow_nodes", mutates_args=("state", "nodes", "rotations", "translations", "edges", "edge_weights", "count"))
+def grow_nodes(state: Tensor, handle: int, points: Tensor, anchors: Tensor, weights: Tensor, valid: Tensor,
+               nodes: Tensor, n_nodes: int, rotations: Tensor, translations: Tensor, edges: Tensor,
+               edge_weights: Tensor, node_coverage: float, min_dist: float, spacing: float, max_new: int,
+               count: Tensor) -> None:
+    """ofx_grow_nodes (new capability; the reference's twin is the host loop of EDGraph.update): new graph nodes at the
+    model rows (points (M,3), anchors i32 (M,4), weights (M,4), valid u8 (M,), as surface_points writes them) that lie
+    more than min_dist from every node, greedily `spacing` apart in row order, at most max_new. The caller's arrays hold
+    n_nodes rows followed by room for max_new more — nodes (.,3), rotations (.,9) or (.,3,3), translations (.,3), edges
+    i32 (.,K_e), edge_weights (.,K_e) — and receive the new rows: position, the translation the point's own skin gives
+    it, the quaternion blend of its anchors' rotations, the K_e nearest other nodes and their weights. count i32 (3,) on
+    the device = [candidates, selected, 1 if the cap cut the selection short]. `handle` is an ofx_grow_create handle
+    sized for at least M rows and max_new nodes; `state` is its ordering token."""
+    M, rows = points.shape[0], int(n_nodes) + int(max_new)
+    for name, t, cols in (("anchors", anchors, 4), ("weights", weights, 4)):
+        if t.shape[0] != M or t.shape[1] != cols:
+            raise ValueError(f"grow_nodes: {name} must be ({M}, {cols}), got {tuple(t.shape)}")
+    if valid.shape[0] != M or count.shape[0] != 3:
+        raise ValueError("grow_nodes: valid must have one entry per row and count three entries")
+    if edges.dim() != 2 or edge_weights.shape != edges.shape:
+        raise ValueError("grow_nodes: edges and edge_weights must be (rows, K_e)")
+    for name, t, per in (("nodes", nodes, 3), ("rotations", rotations, 9), ("translations", translations, 3),
+                         ("edges", edges, edges.shape[1]), ("edge_weights", edge_weights, edges.shape[1])):
+        if t.numel() < rows * per or not t.is_contiguous():
+            raise ValueError(f"grow_nodes: {name} must be contiguous with room for n_nodes + max_new = {rows} rows")
+    call("ofx_grow_nodes", _lib.c_void_p(handle), ptr(points), ptr(anchors), ptr(weights), ptr(valid), M, ptr(nodes),
+         int(n_nodes), ptr(rotations), ptr(translations), ptr(edges), ptr(edge_weights), int(edges.shape[1]),
+         float(node_coverage), float(min_dist), float(spacing), int(max_new), ptr(count), _stream(points))
+
+
+@grow_nodes.register_fake
+def _(state, handle, points, anchors, weights, valid, nodes, n_nodes, rotations, translations, edges, edge_weights,
+      node_coverage, min_dist, spacing, max_new, count):
+    return None
+
+
 # --------------------------------------------------------------------------------------------- dense SPD solve
 @_op("spd_solve", mutates_args=())
 def spd_solve(A: Tensor, b: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
@@ -571,4 +608,4 @@ def _(state, handle, n_nodes, num_iter):
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
-       "rigid_icp", "splat_points", "prepare_depth")
+       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes")

@@ -57,6 +57,7 @@ class FusionPipeline:
         self.int_stream = None
         self._vmodel = None       # track_step(model="volume"): the last sampled volume model (padded device arrays)
         self.model_counts = []    # ... and each sampling's device [accepted, emitted]
+        self._grow_frames = 0     # track_step(grow_every=): volume-model frames tracked with growth switched on
 
     def prepare(self, t):
         """Host-side synthetic inputs of frame t -> device (outside any timed region)."""
@@ -180,8 +181,46 @@ class FusionPipeline:
             splat_radius = default_splat_radius(self.vol._voxel_size, with_normals)
         return dict(occlusion=True, renderer=self._renderer, splat_radius=splat_radius, occl_margin=occl_margin)
 
+    def grow_graph(self, max_model_points=65536, w_min=1.0, resample=False, **grow):
+        """Grow the graph from the fused volume (WarpField.grow_from_volume; **grow: its keywords) under the transforms
+        of the last integrated frame, and let the loop follow: the graph tensors and the previous transforms get the new
+        rows, the solver is replaced by a larger one with the same parameters when the graph outgrows it, and the volume
+        model is sampled again, because skins changed (resample=True: also when no node was added — the loop's frames that
+        left the sampling after their integrate to this call). One host read (the counts). -> grow_from_volume's dict."""
+        M = int(max_model_points)
+        grow.setdefault("max_points", M)
+        grow.setdefault("w_min", w_min)
+        self.flush()
+        if self.int_stream is not None:
+            torch.cuda.current_stream(self.device).wait_stream(self.int_stream)
+        res = self.wf.grow_from_volume(**grow)
+        if res["added"]:
+            wf = self.wf
+            N = wf.num_nodes
+            self.nodes_t = wf.nodes_t
+            self.edges_t = torch.from_numpy(np.ascontiguousarray(wf.graph.edges, np.int32)).to(self.device)
+            self.ew_t = torch.from_numpy(np.ascontiguousarray(wf.graph.edges_weights, np.float32)).to(self.device)
+            self.prev_rot, self.prev_trans = wf.R_t.clone(), wf.T_t.clone()
+            if N > self.solver.max_nodes:
+                old = self.solver
+                self.solver = GaussNewtonSolver(min(max(N, N + N // 2), 16384), old.max_matches, self.device, **old.params)
+        if self._vmodel is not None and (res["added"] or resample):
+            self.sample_model(self._vmodel["points"].shape[0], w_min)
+        return res
+
+    def _motion(self, fi):
+        """fi's motion term for the current graph: inputs sized for the graph before it grew (by track_step(grow_every=)
+        or by grow_graph()) are padded — a new node is its own target (its current position) with confidence 0; inputs
+        of the graph's size are passed on as they are."""
+        tpos, conf = fi.tpos, fi.conf
+        n, N = tpos.shape[0], self.nodes_t.shape[0]
+        if n < N:
+            tpos = torch.cat([tpos, self.nodes_t[n:] + self.prev_trans[n:]])
+            conf = torch.cat([conf, torch.zeros(N - n, dtype=conf.dtype, device=conf.device)])
+        return tpos, conf
+
     def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
-                      occ=(False, None, 0.01), depth_filter=None):
+                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None):
         from .association import ProjectiveAssociator, icp_track
         M = int(max_model_points)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
@@ -197,7 +236,8 @@ class FusionPipeline:
         self.vol.stage(fi.im)
         out, log, _ = icp_track(self._vassoc, self.solver, self.nodes_t, self.edges_t, self.ew_t, m["points"],
                                 m["normals"], m["anchors"], m["weights"], m["valid"], fi.im[-1], self.intr,
-                                self.prev_rot, self.prev_trans, (fi.tpos, fi.conf) if motion else None, icp_iters,
+                                self.prev_rot, self.prev_trans,
+                                self._motion(fi) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M),
                                 depth_filter=depth_filter, **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
         out["assoc"] = log
@@ -206,18 +246,24 @@ class FusionPipeline:
         # integrate, then re-sample in the integrate's stream order; the next association reads the refreshed model, so
         # an overlapped integrate is enqueued now (flush) and this stream waits for it: no integrate / solve overlap here
         done = torch.cuda.Event()
+        due = bool(grow_every) and (self._grow_frames + 1) % int(grow_every) == 0
 
         def resample():
-            self.sample_model(M, w_min)
+            if not due:   # (a frame that grows samples after the growth: the skins change there)
+                self.sample_model(M, w_min)
             done.record()
         self.integrate(fi, t, count_updates, after=resample)
         self.flush()
         torch.cuda.current_stream(self.device).wait_event(done)
+        if grow_every:
+            self._grow_frames += 1
+            if due:
+                out["grow"] = self.grow_graph(M, w_min, resample=True, **(grow or {}))
         return out
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
                    max_model_points=65536, w_min=1.0, rigid_iters=0, occlusion=False, splat_radius=None,
-                   occl_margin=0.01, depth_filter=None, **assoc):
+                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -246,10 +292,19 @@ class FusionPipeline:
 
         depth_filter (both models; None / True / a dict of radius, sigma_s, sigma_r, range_cut): the tracker reads the
         bilateral-filtered frame's vertex map (image_proc.prepare_depth_device) instead of the raw one's; the staged
-        and integrated frame stays the raw one, so the fused volume does not change with the filter itself."""
+        and integrated frame stays the raw one, so the fused volume does not change with the filter itself.
+
+        grow_every > 0 (model="volume" only): after every grow_every-th frame's integrate the graph grows from the fused
+        volume (grow_graph -> WarpField.grow_from_volume; grow: a dict of its keywords), so that surface which first
+        appears in a later frame gets nodes, is fused and becomes a tracking target; the result of such a frame carries
+        "grow": its counts. The graph tensors, the previous transforms, the solver's capacity and the sampled model
+        follow; fi.tpos / fi.conf sized for the graph before it grew are padded (a new node is its own target with
+        confidence 0). One host read per growth. grow_every=0 leaves the loop as it is."""
+        if grow_every and model != "volume":
+            raise ValueError("grow_every needs model='volume': the graph grows from the fused volume")
         if model == "volume":
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
-                                      assoc, (occlusion, splat_radius, occl_margin), depth_filter)
+                                      assoc, (occlusion, splat_radius, occl_margin), depth_filter, grow_every, grow)
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
@@ -262,7 +317,7 @@ class FusionPipeline:
         self.vol.stage(fi.im)
         out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
-                                (fi.tpos, fi.conf) if motion else None, icp_iters,
+                                self._motion(fi) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
                                 depth_filter=depth_filter,
                                 **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),

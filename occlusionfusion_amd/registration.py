@@ -469,6 +469,23 @@ class Registration:
         self.valid_source_verts = np.ones(m["emitted"], bool)
         return m["emitted"]
 
+    def grow_from_volume(self, **kw):
+        """Grow the graph from the fused volume (WarpField.grow_from_volume, its keywords) and follow it: the previous
+        transforms get the new nodes' rows, the solver is replaced by a larger one with the same parameters when the
+        graph outgrows it, and the model is taken from the volume again (update_from_volume with the same max_points /
+        w_min), because skins changed. -> grow_from_volume's dict."""
+        wf = self.warpfield
+        res = wf.grow_from_volume(**kw)
+        if res["added"]:
+            self.graph = wf.graph
+            N = wf.num_nodes
+            self.prev_rot, self.prev_trans = wf.R_t.clone(), wf.T_t.clone()
+            if N > self.solver.max_nodes:
+                old = self.solver
+                self.solver = GaussNewtonSolver(min(max(N, N + N // 2), 16384), old.max_matches, self.device, **old.params)
+        self.update_from_volume(kw.get("max_points", 65536), kw.get("w_min", 1.0))
+        return res
+
     def _intr4(self):
         K = self.intrinsics
         return (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else tuple(K.reshape(-1)[:4])

@@ -224,6 +224,9 @@ class EDGraph:
 
 @dataclass
 class SkinCache:
+    """The bricked skin of the voxel grid. After a full build (skin_tsdf_cache) brick_list is ascending; an in-place
+    update after a graph growth (grow_from_volume) appends the newly qualified bricks at the end, so the list is then no
+    longer ascending — ofx_surface_points and the integrate kernels take lists in any order."""
     brick_list: torch.Tensor   # int32 [n_list] shard-local brick ids
     n_list: int
     anchors: torch.Tensor      # uint16 as int16 storage [n_list*512*4]
@@ -484,6 +487,112 @@ class WarpField:
         res.update(accepted=n_acc, emitted=n_emit, count=out["count"], code=out["code"])
         if with_codes:
             res["histogram"] = [int(x) for x in host[2:2 + len(CODE_NAMES)]]
+        return res
+
+    def _skin_plan(self, nodes, n_old, n_added):
+        """Enqueue ofx_skin_grow_plan for nodes [n_old, n_old + n_added) (n_added: device int32) against the current
+        cache -> (work_bricks, work_slots, counts): device tensors, counts = [re-skinned, appended]. No host read."""
+        t, c = self.tsdf, self._cache
+        nb = max(1, t.n_bricks)
+        wb = torch.empty(nb, dtype=torch.int32, device=self.device)
+        ws = torch.empty(nb, dtype=torch.int32, device=self.device)
+        counts = torch.empty(2, dtype=torch.int32, device=self.device)
+        call("ofx_skin_grow_plan", byref(t.desc), ptr(nodes), int(n_old), ptr(n_added), self.node_coverage, c.k,
+             ptr(c.brick_list), c.n_list, ptr(wb), ptr(ws), ptr(counts), stream_ptr())
+        return wb, ws, counts
+
+    def _skin_apply(self, c, wb, ws, n_re, n_app):
+        """The cache `c` enlarged by n_app slots and re-skinned over the first n_re + n_app work entries against the warp
+        field's current nodes (ofx_skin_grow_apply) -> the new SkinCache. The old cache's tensors are written in place
+        when nothing is appended."""
+        P = _lib.PALETTE
+        n_list = c.n_list + n_app
+
+        def grown(x, per):
+            x = x[:max(1, c.n_list) * per]
+            return x if n_app == 0 else torch.cat([x[:c.n_list * per], torch.empty(n_app * per, dtype=x.dtype, device=x.device)])
+        blist = c.brick_list[:c.n_list] if n_app == 0 else torch.cat([c.brick_list[:c.n_list], wb[n_re:n_re + n_app]])
+        new = SkinCache(blist if n_list else c.brick_list, n_list, grown(c.anchors, 2048), grown(c.weights, 2048), c.k,
+                        grown(c.pal_ids, P), grown(c.pal_n, 1), grown(c.local, 2048))
+        call("ofx_skin_grow_apply", byref(self.tsdf.desc), ptr(self.nodes_t), self.num_nodes, self.node_coverage, c.k,
+             ptr(wb), ptr(ws), n_re + n_app, ptr(new.anchors), ptr(new.weights), ptr(new.pal_ids), ptr(new.pal_n),
+             ptr(new.local), stream_ptr())
+        return new
+
+    def grow_from_volume(self, max_new=256, min_dist=None, spacing=None, max_points=65536, w_min=1.0, incremental=False):
+        """Grow the graph from the fused volume (grow.NodeGrower, ofx_grow_nodes; DynamicFusion's graph update — the
+        reference's route is update_graph(), which its drivers keep commented out): sample the model
+        (surface_points(sync=False)), add a node at every sampled point farther than min_dist (default 2·coverage, the
+        reference's find_unreachable_nodes) from all nodes, greedily `spacing` (default the coverage) apart in row
+        order, at most max_new a call. A new node takes the translation its point's own skin gives it and the
+        quaternion blend of its anchors' rotations, so the warp is continuous across the growth; its edge row holds
+        its nearest other nodes by Euclidean distance (rows of old nodes are kept). graph.nodes / edges /
+        edges_weights / clusters, the transforms, the deformed nodes and the skin cache follow. incremental=True
+        updates the cache in place: only bricks within the cull radius of a new node are skinned again (at their slots)
+        and newly qualified bricks are appended to the list, which is then no longer ascending; the result is a full
+        rebuild's, slot for brick, bit for bit. incremental=False (the default: at config 3's sizes the in-place update measured no
+        faster than the rebuild) rebuilds it in full (skin_tsdf_cache()). Only skin-valid surface points can be candidates, so one call extends the covered surface by a rim of
+        about two coverages; call it after every integrate. One host read (the counts).
+
+        -> dict(added, candidates, capped, reskinned, appended): nodes added, candidate rows, whether max_new cut the
+        selection short, listed bricks skinned again (every listed brick with incremental=False) and bricks that joined the cache's list.
+
+        Raises if no skin cache has been built (skin_tsdf_cache()), or for a sharded volume."""
+        from .grow import MAX_NEW, NodeGrower
+        t = self.tsdf
+        if t.brick_x0 != 0 or t.brick_x1 != (int(t._vol_dim[0]) + 7) // 8 or t.owned_mask is not None:
+            raise ValueError("grow_from_volume needs the whole volume: a sharded TSDFVolume is not supported")
+        if self._cache is None:
+            raise RuntimeError("grow_from_volume needs the skin cache: call skin_tsdf_cache() first")
+        g, N, dev = self.graph, self.num_nodes, self.device
+        max_new = max(0, min(int(max_new), MAX_NEW, 65534 - N))
+        res = dict(added=0, candidates=0, capped=0, reskinned=0, appended=0)
+        if max_new == 0:
+            return res
+        m = self.surface_points(int(max_points), w_min, sync=False)
+        K_e = int(g.edges.shape[1])
+        rows = N + max_new
+        nodes = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        R = torch.empty((rows, 3, 3), dtype=torch.float32, device=dev)
+        T = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        E = torch.full((rows, K_e), -1, dtype=torch.int32, device=dev)
+        W = torch.zeros((rows, K_e), dtype=torch.float32, device=dev)
+        nodes[:N], R[:N], T[:N] = self.nodes_t, self.R_t.reshape(N, 3, 3), self.T_t
+        E[:N], W[:N] = _t(g.edges, dev, torch.int32), _t(g.edges_weights, dev, torch.float32)
+        gw = getattr(self, "_grower", None)
+        if gw is None or gw.max_points < int(max_points) or gw.max_new < max_new:
+            gw = self._grower = NodeGrower(int(max_points), max_new, dev)
+        count = gw.grow(m["points"], m["anchors"], m["weights"], m["valid"], nodes, N, R, T, E, W, self.node_coverage,
+                        min_dist, spacing, max_new)
+        old = self._cache
+        incremental = bool(incremental) and old.k == 4 and old.pal_n is not None
+        if incremental:
+            wb, ws, pc = self._skin_plan(nodes, N, count[1:2])
+            n_cand, n_sel, capped, n_re, n_app = (int(v) for v in torch.cat([count, pc]).cpu().tolist())   # the one host read
+        else:
+            n_cand, n_sel, capped = (int(v) for v in count.cpu().tolist())   # the one host read
+        res.update(candidates=n_cand, capped=capped)
+        if n_sel == 0:
+            return res
+        n = N + n_sel
+        n_list_old = self._cache.n_list
+        g.nodes = nodes[:n].cpu().numpy()
+        g.edges, g.edges_weights = E[:n].cpu().numpy(), W[:n].cpu().numpy()
+        g.edges_distances = np.concatenate([g.edges_distances, np.zeros((n_sel, K_e), np.float32)], 0)
+        g.node_indices = np.concatenate([g.node_indices, -np.ones((n_sel, 1), np.int32)], 0)
+        g.num_nodes = n
+        g.compute_clusters()
+        deformed = np.concatenate([np.asarray(self.deformed_nodes, np.float32).reshape(-1, 3)[:N],
+                                   (nodes[N:n] + T[N:n]).cpu().numpy()], 0)
+        self._set_graph(g)
+        self.set_node_transforms(R[:n].clone(), T[:n].clone())
+        self.deformed_nodes = deformed
+        if incremental:
+            c = self._cache = self._skin_apply(old, wb, ws, n_re, n_app)
+            res.update(added=n_sel, reskinned=n_re, appended=n_app)
+        else:
+            c = self.skin_tsdf_cache()
+            res.update(added=n_sel, reskinned=c.n_list, appended=c.n_list - n_list_old)
         return res
 
     def render_live(self, max_points=65536, w_min=1.0, splat_radius=None, intr=None, height=None, width=None):
