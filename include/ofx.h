@@ -54,6 +54,10 @@
  *   ofx_prepare_depth       (new) bilateral-filtered depth of a frame, its vertex map and its normal map: what the depth
  *                           tracker reads the live frame through — (no reference twin: the reference has no depth filter.
  *                           Parity unpinned; restated op for op by tests/prepare_ref.py)
+ *   ofx_photo_associate     (new) photometric correspondence search: each warped model point's best colour match in a window
+ *                           of the live frame, among the pixels that pass ofx_associate's gates — (no reference twin: the
+ *                           reference's dense matches come from a learned flow network. Parity unpinned; restated op for
+ *                           op by tests/photo_ref.py)
  *   ofx_depth_to_pc         Registration.optimize target cloud: depth_2_pc, NonRigidICP/model/geometry.py:44-59,
  *                           mask compaction, map_pixel_to_pcd              registration_fusion.py:104-109,388-395
  *   ofx_pixel_anchors_euclidean  csrc compute_pixel_anchors_euclidean     csrc/cpu/graph_proc.cpp:610-709
@@ -498,6 +502,50 @@ typedef struct ofx_prepare_params {
 int ofx_prepare_depth(const void* depth, int32_t is_u16, int32_t height, int32_t width, const ofx_camera* cam,
                       const ofx_prepare_params* prm, float* depth_out, float* point_image, float* normal_image,
                       ofx_stream_t s);
+
+/* ---------------- Photometric correspondence search (new capability; the reference has none — parity unpinned) ----------------
+ * The stand-in for the reference's flow network, as ofx_associate is for its landmark matcher: each warped model point looks in
+ * a (2*radius + 1)^2 window around its own pixel for the live pixel whose colour matches its own best, among the pixels that
+ * pass ofx_associate's geometric gates; that pixel's vertex is the point's 3-D target (a tangential constraint for the
+ * solver's existing 3-D rows). Takes an ofx_assoc handle and reuses its scratch. Restated op for op by tests/photo_ref.py.
+ * Arithmetic: f32, no contraction, every step fixed.
+ *   x', n', the pixel (u, v) and the codes 1 and 2 are ofx_associate's (the same device code)
+ *   taps: dv = -radius..radius (outer), du = -radius..radius (inner); a tap off the image is skipped (the centre never is).
+ *         At a tap, q = point_image, n_q = normal_image, c = color_image at (u + du, v + dv) (planar f32[3*H*W] each;
+ *         normal_image as ofx_prepare_depth writes it for point_image: zeros where the gate has no normal)
+ *   tap code, the first that applies:
+ *     3  !(q_z > 0)
+ *     4  n_q is all zero
+ *     5  d2 > dist_max^2, d2 = (e_x^2 + e_y^2) + e_z^2, e = q - x'
+ *     6  normals given and n'.n_q < cos_min (summed (x + y) + z)
+ *     7  !(c2 <= color_max^2), c2 = (dr^2 + dg^2) + db^2, d. = c. - colors[p]. (a NaN colour lands here)
+ *     0  eligible, with cost E = c2 + geo_weight*d2 (the product rounded, then the sum)
+ *   point: any tap eligible -> code 0, the match is the eligible tap of the smallest E, ties to the first in tap order; tgt =
+ *         its q, pixel = its (u + du, v + dv), cost = its E. Otherwise the code is the LARGEST tap code (how far any tap
+ *         got; a maximum, so independent of the order) and tgt = 0, pixel = (-1, -1), cost = 0, as for codes 1 and 2.
+ * Compaction is ofx_associate's (scan of code == 0, the 64-bit rank-thinning rule, ascending point order, rows past `emitted`
+ * left untouched), with pixel_out f32[max_matches,2] = the match pixel — what the solver's target_px / target_py rows take.
+ * With radius = 0, color_max = +inf and normal_image = ofx_prepare_depth's (radius 0, the same edge_max) of point_image,
+ * code, tgt, warped, count and the compacted arrays equal ofx_associate's in OFX_ASSOC_POINT mode byte for byte.
+ * colors f32[P,3] (rgb in [0,1]) is required; normals, valid, warped, pixel, cost and pixel_out may be NULL (pixel_out needs
+ * pixel). Null buffers, alignment and the camera / image size are checked as in ofx_associate; also OFX_ERR_ARG: radius
+ * outside [0, OFX_PHOTO_RMAX], geo_weight negative or non-finite, a NaN color_max, n_points above the handle's.
+ * n_points = 0 is legal: count = [0, 0]. Stream-ordered: no allocation and no host sync inside the call. */
+typedef struct ofx_photo_params {
+  float dist_max, cos_min;   /* ofx_associate's gates, same meaning, applied to every tap */
+  float color_max;           /* a tap is eligible only if its colour distance^2 <= color_max^2 (+inf: off) */
+  float geo_weight;          /* 1/m^2: cost = c2 + geo_weight*d2 (>= 0, finite) */
+  int32_t radius;            /* 0 .. OFX_PHOTO_RMAX: window (2r+1)^2 around the point's pixel */
+  int32_t max_matches;       /* rows of the compacted outputs */
+} ofx_photo_params;
+#define OFX_PHOTO_RMAX 8
+int ofx_photo_associate(void* assoc_handle, const float* points, const float* normals, const float* colors,
+                        const int32_t* anchors, const float* weights, const uint8_t* valid, int64_t n_points,
+                        const float* packed_nodes, int32_t n_nodes, const ofx_camera* cam, const float* point_image,
+                        const float* normal_image, const float* color_image, int32_t height, int32_t width,
+                        const ofx_photo_params* prm, uint8_t* code, float* tgt, float* warped, int32_t* pixel,
+                        float* cost, int32_t* match_idx, float* src_out, float* tgt_out, int32_t* anchors_out,
+                        float* weights_out, float* pixel_out, int32_t* count, ofx_stream_t s);
 
 /* ---------------- Skinned surface points of the TSDF (new capability; the reference has none — parity unpinned) ----------------
  * The tracking model read off the volume itself: canonical surface points, their outward normals and their anchors and

@@ -31,6 +31,14 @@ class AssocParams(ctypes.Structure):
                 ("max_matches", c_int32), ("_pad", c_int32)]
 
 
+class PhotoParams(ctypes.Structure):
+    _fields_ = [("dist_max", c_float), ("cos_min", c_float), ("color_max", c_float), ("geo_weight", c_float),
+                ("radius", c_int32), ("max_matches", c_int32)]
+
+
+PHOTO_RMAX = 8   # OFX_PHOTO_RMAX (include/ofx.h)
+
+
 class RigidParams(ctypes.Structure):
     _fields_ = [("dist_max", c_float), ("cos_min", c_float), ("edge_max", c_float), ("iters", c_int32),
                 ("min_matches", c_int32), ("damping", c_double), ("stop_twist", c_double)]
@@ -114,6 +122,8 @@ _SIGS = {
     "ofx_assoc_create": [c_int64, P],
     "ofx_assoc_destroy": [P],
     "ofx_associate": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P],
+    "ofx_photo_associate": [P, P, P, P, P, P, P, c_int64, P, c_int32, P, P, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P,
+                            P, P, P, P, P],
     "ofx_rigid_create": [c_int64, P],
     "ofx_rigid_destroy": [P],
     "ofx_rigid_icp": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P],

@@ -10,7 +10,10 @@ FusionPipeline.track_step share; RigidAligner (torch.ops.ofx.rigid_icp -> ofx_ri
 rigid point-to-plane ICP of all model points whose pose fold_rigid folds into the node transforms. This is the data term for what the camera sees: motion of occluded nodes still needs the
 motion-completion input. ModelRenderer (torch.ops.ofx.splat_points -> ofx_splat_points) is the model's own z-buffer in the
 live frame: with occlusion=True, icp_track keeps the points that the model itself hides out of both stages, and
-WarpField.render_live shows the fused model where the camera is.
+WarpField.render_live shows the fused model where the camera is. ProjectiveAssociator.associate_photo
+(torch.ops.ofx.photo_associate -> ofx_photo_associate) is the search by colour — the stand-in for the reference's flow
+net: with photo=True, icp_track matches every point to the best colour match in a window around its pixel, which follows
+motion along a surface that depth alone cannot see.
 """
 import numpy as np
 import torch
@@ -20,7 +23,9 @@ from ._lib import byref, call
 
 MODES = {"point": 0, "plane": 1}
 CODE_NAMES = ("accepted", "invalid_skin", "off_image", "hole", "no_normal", "too_far", "normal_mismatch")
+PHOTO_CODE_NAMES = CODE_NAMES + ("colour",)   # associate_photo's codes: associate's, and 7
 ASSOC_DEFAULTS = dict(dist_max=0.05, cos_min=0.5, edge_max=0.03, mode="plane", max_matches=10000)
+PHOTO_DEFAULTS = dict(radius=4, color_max=float("inf"), geo_weight=1.0)
 
 
 class TooFewMatches(RuntimeError):
@@ -128,6 +133,40 @@ class ProjectiveAssociator(_Handle):
         self.last = {"match_idx": midx[:n_emit], "src": src[:n_emit], "tgt": tgt[:n_emit], "anchors": a_o[:n_emit],
                      "weights": w_o[:n_emit], "code": code, "tgt_all": tgt_all, "warped": warped, "accepted": n_acc,
                      "emitted": n_emit, "histogram": [int(x) for x in host[2:2 + len(CODE_NAMES)]]}
+        return self.last
+
+
+    def associate_photo(self, points, normals, colors, anchors, weights, valid, warpfield_or_packed_nodes, point_image,
+                        normal_image, color_image, intr, dist_max=0.05, cos_min=0.5, color_max=float("inf"),
+                        geo_weight=1.0, radius=4, max_matches=10000):
+        """Photometric correspondence search (torch.ops.ofx.photo_associate -> ofx_photo_associate): inputs as
+        `associate`, plus the points' colours (P,3) rgb in [0,1], the frame's normal map normal_image (3,H,W)
+        (prepare_depth_device of the same frame: zeros where the gate has no normal) and its colour image color_image
+        (3,H,W) rgb in [0,1]. Every point searches the (2·radius + 1)² window around its pixel (radius 0..8) for the
+        pixel that passes associate's gates (dist_max, cos_min; a colour farther than color_max is refused too) with the
+        smallest cost |Δcolour|² + geo_weight·|q − x'|²; that pixel's vertex is the target.
+
+        Returns associate's dict (code 7 = "colour": PHOTO_CODE_NAMES; the histogram has one more entry), plus pixel
+        (emitted rows, f32 (u, v) of the match: what the solver's target_px / target_py take), pixel_all i32 (P,2) and
+        cost (P,). The same single host read."""
+        d = self.device
+        pts, nrm, a, w, v, packed, P = _skinned(points, normals, anchors, weights, valid, warpfield_or_packed_nodes, d,
+                                                self.max_points, "associator")
+        col = _f32(colors, d, (P, 3))
+        vm, nm, cm = _f32(point_image, d), _f32(normal_image, d), _f32(color_image, d)
+        assert vm.dim() == 3 and vm.shape[0] == 3, "point image must be (3, H, W)"
+        assert nm.shape == vm.shape and cm.shape == vm.shape, "normal and colour image must match the point image"
+        out = torch.ops.ofx.photo_associate(self._state, self._h.value, pts, nrm, col, a, w, v, packed, vm, nm, cm,
+                                            [float(x) for x in intr[:4]], float(dist_max), float(cos_min),
+                                            float(color_max), float(geo_weight), int(radius), int(max_matches))
+        code, tgt_all, warped, pixel_all, cost, midx, src, tgt, a_o, w_o, px_o, count = out
+        hist = torch.bincount(code.to(torch.int64), minlength=len(PHOTO_CODE_NAMES))
+        host = torch.cat([count.to(torch.int64), hist]).cpu().tolist()   # the one host sync
+        n_acc, n_emit = int(host[0]), int(host[1])
+        self.last = {"match_idx": midx[:n_emit], "src": src[:n_emit], "tgt": tgt[:n_emit], "anchors": a_o[:n_emit],
+                     "weights": w_o[:n_emit], "pixel": px_o[:n_emit], "code": code, "tgt_all": tgt_all,
+                     "warped": warped, "pixel_all": pixel_all, "cost": cost, "accepted": n_acc, "emitted": n_emit,
+                     "histogram": [int(x) for x in host[2:2 + len(PHOTO_CODE_NAMES)]]}
         return self.last
 
 
@@ -259,10 +298,24 @@ def fold_rigid(nodes, rot, trans, pose):
     return Rn.to(torch.float32).contiguous(), Tn.to(torch.float32).contiguous()
 
 
+def photo_params(photo):
+    """The photo= keyword of the tracking layers as associate_photo's keywords: None / False -> None (off), True ->
+    PHOTO_DEFAULTS, a dict of radius / color_max / geo_weight -> the defaults with those; another key is a TypeError."""
+    if photo is None or photo is False:
+        return None
+    pho = dict(PHOTO_DEFAULTS)
+    if photo is not True:
+        unknown = set(photo) - set(pho)
+        if unknown:
+            raise TypeError(f"unknown photo parameters {sorted(unknown)}")
+        pho.update(photo)
+    return pho
+
+
 def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
               valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3,
               rigid_iters=0, rigid=None, occlusion=False, renderer=None, splat_radius=None, occl_margin=0.01,
-              depth_filter=None, **assoc):
+              depth_filter=None, photo=None, colors=None, color_image=None, **assoc):
     """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
     associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
     matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
@@ -287,7 +340,16 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     frame is prepared first (image_proc.prepare_depth_device with its defaults: the bilateral-filtered depth's vertex
     map); a dict overrides radius / sigma_s / sigma_r / range_cut (another key is a TypeError). The prepared vertex map
     is what the rigid stage and every association read and what is returned as the third value; the association's own
-    edge_max keeps governing the gate, and the z-buffer stage does not read the frame."""
+    edge_max keeps governing the gate, and the z-buffer stage does not read the frame.
+
+    photo: None — the loop as it was; True, or a dict of radius / color_max / geo_weight (PHOTO_DEFAULTS; another key is
+    a TypeError) — every iteration calls ProjectiveAssociator.associate_photo in place of associate: each point's target
+    is the vertex of the best colour match in a window around its pixel, which also constrains motion along the surface
+    that depth alone cannot see. It needs the model's colours `colors` (P,3) and the frame's colour image `color_image`
+    (3,H,W), both rgb in [0,1] (a ValueError without them, before any device work). The frame's normal map comes from
+    prepare_depth_device with the association's edge_max: radius 0 without depth_filter (its vertex map is then the raw
+    one bit for bit), the filter's settings with it. `mode` is ignored under photo: the target is always the vertex.
+    The rigid stage and the occlusion gate work as before."""
     from .image_proc import PREPARE_DEFAULTS, backproject_depth_device, prepare_depth_device
     rigid_iters = int(rigid_iters)
     if rigid_iters < 0:
@@ -306,6 +368,9 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
             if unknown:
                 raise TypeError(f"unknown depth_filter parameters {sorted(unknown)}")
             filt.update(depth_filter)
+    pho = photo_params(photo)
+    if pho is not None and (colors is None or color_image is None):
+        raise ValueError("photo needs the model's colours (colors=...) and the frame's colour image (color_image=...)")
     d = solver.device
     prm = dict(ASSOC_DEFAULTS)
     unknown = set(assoc) - set(prm)
@@ -317,7 +382,15 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     fx, fy, cx, cy = (float(v) for v in intr[:4])
     dep = depth if isinstance(depth, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(depth, np.float32))
     dep = dep.to(device=d, dtype=torch.float32)
-    if filt is None:
+    nm = cim = None
+    if pho is not None:
+        prep = prepare_depth_device(dep, fx, fy, cx, cy, normals=True, edge_max=float(prm["edge_max"]),
+                                    **(filt if filt is not None else dict(PREPARE_DEFAULTS, radius=0)))
+        vm, nm = prep["point_image"], prep["normals"]
+        cim = _f32(color_image, d)
+        if cim.shape != vm.shape:
+            raise ValueError(f"color_image must be {tuple(vm.shape)}, got {tuple(cim.shape)}")
+    elif filt is None:
         vm = backproject_depth_device(dep, fx, fy, cx, cy)
     else:
         vm = prepare_depth_device(dep, fx, fy, cx, cy, normals=False, **filt)["point_image"]
@@ -351,11 +424,16 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         v_stage = valid
         if occlusion:
             v_stage, ren = seen(packed)
-        m = associator.associate(points, normals, anchors, weights, v_stage, packed, vm, (fx, fy, cx, cy), **prm)
+        if pho is None:
+            m = associator.associate(points, normals, anchors, weights, v_stage, packed, vm, (fx, fy, cx, cy), **prm)
+        else:
+            m = associator.associate_photo(points, normals, colors, anchors, weights, v_stage, packed, vm, nm, cim,
+                                           (fx, fy, cx, cy), dist_max=prm["dist_max"], cos_min=prm["cos_min"],
+                                           max_matches=prm["max_matches"], **pho)
         log.append({"accepted": m["accepted"], "emitted": m["emitted"], "histogram": m["histogram"]})
         if m["emitted"] < 16:
             raise TooFewMatches(f"projective association {it} emitted {m['emitted']} matches of {m['accepted']} accepted "
-                                f"({dict(zip(CODE_NAMES, m['histogram']))}); at least 16 (4·K) are needed to solve")
+                                f"({dict(zip(PHOTO_CODE_NAMES, m['histogram']))}); at least 16 (4·K) are needed to solve")
         out = solver.optimize(graph_nodes, graph_edges, graph_edges_weights, tloc, tconf, m["src"], m["anchors"],
                               m["weights"], m["tgt"], (fx, fy, cx, cy), prev_rot=rot, prev_trans=trans)
         rot, trans = out["node_rotations"], out["node_translations"]

@@ -22,17 +22,11 @@
 // thinned evenly and deterministically (rank r is kept iff floor((r+1)·max/n) > floor(r·max/n), 64-bit), where the
 // reference draws an unseeded randperm (model/model.py:319-334).
 #include "ofx_common.h"
+#include "assoc_handle.h"
 #include "gate_device.h"
 #include "scan_flags.h"
 
 namespace ofx {
-
-struct Assoc {
-  int64_t cap = 0;
-  uint8_t* flag = nullptr;   // [cap] 1 = accepted
-  int32_t* rank = nullptr;   // [cap + 1] exclusive ranks of the accepted points, their number at [n]
-  int32_t* tsum = nullptr;   // [scan_tiles(cap) + 1]
-};
 
 // VALID / NRM: valid / normals given (compile-time, so that trip 1 is branch-free)
 template <bool VALID, bool NRM>

@@ -118,6 +118,24 @@ __device__ __forceinline__ int proj_gate(const CamD& c, const float* __restrict_
   return 0;
 }
 
+// The gate of one window tap of photo.hip against the warped point in s: the tap's vertex q, its normal n_q as
+// ofx_prepare_depth wrote it (zeros where vertex_normal has none) and its colour difference (dr, dg, db) to the point ->
+// the first code of 3..7 that applies, or 0; d2 = |q - point|² and c2 = |colour difference|² are filled in either way.
+template <bool NRM>
+__device__ __forceinline__ int tap_gate(const SkinPt& s, float qx, float qy, float qz, float nx, float ny, float nz,
+                                        float dr, float dg, float db, float dist_max2, float cos_min, float color_max2,
+                                        float& d2, float& c2) {
+  const float ex = qx - s.x, ey = qy - s.y, ez = qz - s.z;
+  d2 = (ex * ex + ey * ey) + ez * ez;
+  c2 = (dr * dr + dg * dg) + db * db;
+  if (!(qz > 0.f)) return 3;
+  if (nx == 0.f && ny == 0.f && nz == 0.f) return 4;
+  if (d2 > dist_max2) return 5;
+  if (NRM && dot3(s.nx, s.ny, s.nz, nx, ny, nz) < cos_min) return 6;
+  if (!(c2 <= color_max2)) return 7;
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------- host part
 // The argument checks the three entry points share, for n_points > 0. more: the entry point's further required buffers
 // are all there; align16: its further pointers (or-ed) that must be 16-byte aligned.

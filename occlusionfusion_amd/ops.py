@@ -234,6 +234,63 @@ def _(state, handle, points, normals, anchors, weights, valid, packed_nodes, poi
             points.new_empty((2,), dtype=i))
 
 
+# --------------------------------------------------------------------------------------------- photometric association
+@_op("photo_associate", mutates_args=("state",))
+def photo_associate(state: Tensor, handle: int, points: Tensor, normals: Optional[Tensor], colors: Tensor,
+                    anchors: Tensor, weights: Tensor, valid: Optional[Tensor], packed_nodes: Tensor,
+                    point_image: Tensor, normal_image: Tensor, color_image: Tensor, intr: List[float], dist_max: float,
+                    cos_min: float, color_max: float, geo_weight: float, radius: int, max_matches: int
+                    ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor,
+                               Tensor]:
+    """ofx_photo_associate (new capability, no reference twin): for every point (P,3) with colour colors (P,3) — skinned
+    and warped as in `associate` — the best colour match in the (2·radius + 1)² window around its pixel among the pixels
+    of point_image / normal_image / color_image (3,H,W each) that pass associate's gates -> per point code u8 (P,) (0 =
+    matched, 1..7), tgt (P,3), warped (P,3), pixel i32 (P,2), cost (P,); compacted, at their full max_matches size (rows
+    past count[1] are zero): match_idx i32, src (.,3), tgt (.,3), anchors i32 (.,4), weights (.,4), pixel (.,2) f32; count
+    int32[2] on the device = [accepted, emitted]. `handle` is an ofx_assoc_create handle sized for at least P points;
+    `state` is its ordering token (its scratch is hidden state)."""
+    P, M = points.shape[0], int(max_matches)
+    dev = points.device
+    _, H, W = point_image.shape
+    if normal_image.shape != point_image.shape or color_image.shape != point_image.shape:
+        raise ValueError("photo_associate: point, normal and colour image must all be (3, H, W)")
+    if colors.shape[0] != P or colors.shape[1] != 3:
+        raise ValueError(f"photo_associate: colors must be ({P}, 3), got {tuple(colors.shape)}")
+    cam = _camera(intr, H, W)
+    prm = _lib.PhotoParams(float(dist_max), float(cos_min), float(color_max), float(geo_weight), int(radius), M)
+    v = None if valid is None else valid.to(torch.uint8)
+    f, i = torch.float32, torch.int32
+    code = torch.empty(P, dtype=torch.uint8, device=dev)
+    tgt = torch.empty((P, 3), dtype=f, device=dev)
+    warped = torch.empty((P, 3), dtype=f, device=dev)
+    pixel = torch.empty((P, 2), dtype=i, device=dev)
+    cost = torch.empty(P, dtype=f, device=dev)
+    midx = torch.zeros(M, dtype=i, device=dev)
+    src_o = torch.zeros((M, 3), dtype=f, device=dev)
+    tgt_o = torch.zeros((M, 3), dtype=f, device=dev)
+    a_o = torch.zeros((M, 4), dtype=i, device=dev)
+    w_o = torch.zeros((M, 4), dtype=f, device=dev)
+    px_o = torch.zeros((M, 2), dtype=f, device=dev)
+    count = torch.empty(2, dtype=i, device=dev)
+    call("ofx_photo_associate", _lib.c_void_p(handle), ptr(points), ptr(normals), ptr(colors), ptr(anchors),
+         ptr(weights), ptr(v), P, ptr(packed_nodes), packed_nodes.shape[0], byref(cam), ptr(point_image),
+         ptr(normal_image), ptr(color_image), H, W, byref(prm), ptr(code), ptr(tgt), ptr(warped), ptr(pixel), ptr(cost),
+         ptr(midx), ptr(src_o), ptr(tgt_o), ptr(a_o), ptr(w_o), ptr(px_o), ptr(count), _stream(points))
+    return code, tgt, warped, pixel, cost, midx, src_o, tgt_o, a_o, w_o, px_o, count
+
+
+@photo_associate.register_fake
+def _(state, handle, points, normals, colors, anchors, weights, valid, packed_nodes, point_image, normal_image,
+      color_image, intr, dist_max, cos_min, color_max, geo_weight, radius, max_matches):
+    P, M = points.shape[0], int(max_matches)
+    f, i = torch.float32, torch.int32
+    return (points.new_empty((P,), dtype=torch.uint8), points.new_empty((P, 3), dtype=f),
+            points.new_empty((P, 3), dtype=f), points.new_empty((P, 2), dtype=i), points.new_empty((P,), dtype=f),
+            points.new_empty((M,), dtype=i), points.new_empty((M, 3), dtype=f), points.new_empty((M, 3), dtype=f),
+            points.new_empty((M, 4), dtype=i), points.new_empty((M, 4), dtype=f), points.new_empty((M, 2), dtype=f),
+            points.new_empty((2,), dtype=i))
+
+
 # --------------------------------------------------------------------------------------------- rigid pre-alignment
 @_op("rigid_icp", mutates_args=("state", "pose"))
 def rigid_icp(state: Tensor, handle: int, points: Tensor, normals: Optional[Tensor], anchors: Tensor, weights: Tensor,
@@ -608,4 +665,4 @@ def _(state, handle, n_nodes, num_iter):
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
-       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes")
+       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate")

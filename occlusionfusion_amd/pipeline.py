@@ -72,6 +72,29 @@ class FusionPipeline:
     def integrate_source(self, fi):
         self.vol.integrate({"im": fi.im, "id": 0})
         self.wf.skin_tsdf_cache()
+        self.set_source_colors(fi.im)
+
+    def set_source_colors(self, im):
+        """Keep the source frame's rgb planes (a reference, no copy, no device work): what track_step(model=
+        "canonical", photo=...) colours the canonical points with, at their own pixels."""
+        self._source_rgb = im[:3]
+        self._ccolors = None
+
+    def _canonical_colors(self):
+        """(P,3) f32 rgb of seq.canonical_points: the source frame's colour at each point's pixel (the rounded
+        projection, clamped into the image), computed once."""
+        if getattr(self, "_ccolors", None) is None:
+            rgb = self._source_rgb
+            rgb = rgb if isinstance(rgb, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rgb, np.float32))
+            rgb = rgb.to(self.device, torch.float32)
+            p = torch.from_numpy(np.ascontiguousarray(self.seq.canonical_points, np.float32)).to(self.device)
+            fx, fy, cx, cy = (float(x) for x in self.intr[:4])
+            H, W = int(rgb.shape[1]), int(rgb.shape[2])
+            z = p[:, 2].clamp(min=1e-6)
+            u = torch.round(p[:, 0] * fx / z + cx).long().clamp(0, W - 1)
+            v = torch.round(p[:, 1] * fy / z + cy).long().clamp(0, H - 1)
+            self._ccolors = rgb[:, v, u].t().contiguous()
+        return self._ccolors
 
     def problem(self, fi):
         """Frame fi's GN problem as GaussNewtonSolver.optimize(prefetch=) takes it."""
@@ -220,8 +243,8 @@ class FusionPipeline:
         return tpos, conf
 
     def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
-                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None):
-        from .association import ProjectiveAssociator, icp_track
+                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None, photo=None):
+        from .association import ProjectiveAssociator, icp_track, photo_params
         M = int(max_model_points)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
             self._vassoc = ProjectiveAssociator(M, self.device)
@@ -232,6 +255,13 @@ class FusionPipeline:
             self.model_counts = []
             self.sample_model(M, w_min)       # the volume as integrate_source (or the frames so far) left it
         m = self._vmodel
+        pho = {}
+        if photo_params(photo) is not None:
+            if not self.vol.with_color:
+                raise ValueError("photo needs the model's colours: the volume does not fuse colour")
+            if "colors" not in m:   # the sampled points' fused colours, once per sampling
+                self.wf.surface_colors(m)
+            pho = dict(photo=photo, colors=m["colors"], color_image=fi.im[:3])
         assoc.setdefault("max_matches", self.n_matches)
         self.vol.stage(fi.im)
         out, log, _ = icp_track(self._vassoc, self.solver, self.nodes_t, self.edges_t, self.ew_t, m["points"],
@@ -239,7 +269,7 @@ class FusionPipeline:
                                 self.prev_rot, self.prev_trans,
                                 self._motion(fi) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M),
-                                depth_filter=depth_filter, **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
+                                depth_filter=depth_filter, **pho, **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out
@@ -263,7 +293,7 @@ class FusionPipeline:
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
                    max_model_points=65536, w_min=1.0, rigid_iters=0, occlusion=False, splat_radius=None,
-                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, **assoc):
+                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -299,15 +329,32 @@ class FusionPipeline:
         appears in a later frame gets nodes, is fused and becomes a tracking target; the result of such a frame carries
         "grow": its counts. The graph tensors, the previous transforms, the solver's capacity and the sampled model
         follow; fi.tpos / fi.conf sized for the graph before it grew are padded (a new node is its own target with
-        confidence 0). One host read per growth. grow_every=0 leaves the loop as it is."""
+        confidence 0). One host read per growth. grow_every=0 leaves the loop as it is.
+
+        photo (both models; None / True / a dict of radius, color_max, geo_weight): every association is the
+        photometric search (ProjectiveAssociator.associate_photo): a point's target is the vertex of the best colour
+        match in a window around its pixel, so that motion along the surface, which depth alone cannot see, is
+        followed. The frame's colour image is fi.im[:3] (rgb in [0,1]). The volume model's colours are the fused ones
+        (TSDFVolume.voxel_rgb of the sampled voxels); the canonical points take the source frame's rgb at their own
+        pixels (set_source_colors(im), called by integrate_source; a ValueError without it, before any device work).
+        `mode` is ignored then: the target is always the vertex. None leaves the loop as it is."""
+        from .association import photo_params
+        photo_params(photo)   # (an unknown key is a TypeError before anything is touched)
         if grow_every and model != "volume":
             raise ValueError("grow_every needs model='volume': the graph grows from the fused volume")
         if model == "volume":
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
-                                      assoc, (occlusion, splat_radius, occl_margin), depth_filter, grow_every, grow)
+                                      assoc, (occlusion, splat_radius, occl_margin), depth_filter, grow_every, grow,
+                                      photo)
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
+        pho = {}
+        if photo_params(photo) is not None:
+            if getattr(self, "_source_rgb", None) is None:
+                raise ValueError("photo needs the model's colours: integrate_source(fi) (or set_source_colors(im)) "
+                                 "takes them from the source frame")
+            pho = dict(photo=photo, colors=self._canonical_colors(), color_image=fi.im[:3])
         if getattr(self, "_track", None) is None:
             pts = torch.from_numpy(np.ascontiguousarray(self.seq.canonical_points, np.float32)).to(self.device)
             a, w, v = self.wf.skin_device(pts)
@@ -319,7 +366,7 @@ class FusionPipeline:
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
                                 self._motion(fi) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
-                                depth_filter=depth_filter,
+                                depth_filter=depth_filter, **pho,
                                 **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),
                                 **assoc)
         out["assoc"] = log

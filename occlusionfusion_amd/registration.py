@@ -440,8 +440,9 @@ class Registration:
         self.prev_trans = None
         self.update(canonical_vertices)
 
-    def update(self, canonical_vertices):
-        """registration_fusion.py:66-85: skin the canonical vertices, keep the valid ones."""
+    def update(self, canonical_vertices, colors=None):
+        """registration_fusion.py:66-85: skin the canonical vertices, keep the valid ones. colors: optional rgb in [0,1]
+        of the vertices, (V,3): kept for the valid ones as source_colors, what track(photo=...) matches with."""
         a, w, v = self.warpfield.skin_device(canonical_vertices)
         self.valid_source_verts = v.cpu().numpy()
         vt = torch.as_tensor(np.ascontiguousarray(canonical_vertices, np.float32), device=self.device)
@@ -449,6 +450,10 @@ class Registration:
         self.point_anchors = a[v]
         self.anchor_weight = w[v]
         self.source_normals = None   # (set by update_from_volume only: caller-given vertices carry no normals)
+        self.source_colors = None
+        if colors is not None:
+            self.source_colors = torch.as_tensor(np.ascontiguousarray(colors, np.float32),
+                                                 device=self.device).reshape(-1, 3)[v]
 
     def update_from_volume(self, max_points=None, w_min=1.0):
         """The model from the fused volume instead of caller-given vertices (the reference's per-frame
@@ -457,11 +462,13 @@ class Registration:
         skin the integrate warps them with — becomes source_pcd / point_anchors / anchor_weight, every point valid, and
         source_normals holds their unit normals, which track() then gates with. max_points: None keeps every accepted
         voxel (one more host read to size the arrays), else they are thinned evenly to at most that many. Needs the
-        warp field's skin cache (skin_tsdf_cache()). -> the number of model points."""
+        warp field's skin cache (skin_tsdf_cache()). A volume that fuses colour also gives source_colors: the points'
+        fused rgb (TSDFVolume.voxel_rgb), what track(photo=...) matches with. -> the number of model points."""
         wf = self.warpfield
         if max_points is None:
             max_points = wf.surface_points(0, w_min)["accepted"]
         m = wf.surface_points(int(max_points), w_min)
+        self.source_colors = wf.surface_colors(m) if getattr(wf.tsdf, "with_color", False) else None
         self.source_pcd = m["points"].clone()
         self.point_anchors = m["anchors"].clone()
         self.anchor_weight = m["weights"].clone()
@@ -520,7 +527,8 @@ class Registration:
         return res
 
     def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
-              rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, depth_filter=None, **assoc):
+              rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, depth_filter=None, photo=None,
+              **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -543,8 +551,22 @@ class Registration:
         has "render": the last render's dict of device tensors. No host synchronisation is added.
         depth_filter (None / True / a dict of radius, sigma_s, sigma_r, range_cut): the rigid stage and the associations
         read the bilateral-filtered frame's vertex map (image_proc.prepare_depth_device) instead of the raw one's; tgt_pcd
-        / pix_2_pcd are still the raw depth's. None is the loop as it was."""
-        from .association import ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track
+        / pix_2_pcd are still the raw depth's. None is the loop as it was.
+        photo (None / True / a dict of radius, color_max, geo_weight): every association is the photometric search
+        (ProjectiveAssociator.associate_photo, ofx_photo_associate) — each point's target is the vertex of the best
+        colour match in a window around its pixel, among the pixels that pass the geometric gates — which also follows
+        motion along the surface that depth alone cannot see. The frame's colour image is im[:3] (rgb in [0,1]); the
+        model's colours are source_colors (update(colors=...), or update_from_volume() of a volume that fuses colour):
+        without them a ValueError, before any device work. `mode` is ignored then: the target is always the vertex.
+        None is the loop as it was."""
+        from .association import (ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track,
+                                  photo_params)
+        pho = {}
+        if photo_params(photo) is not None:
+            if getattr(self, "source_colors", None) is None:
+                raise ValueError("photo needs the model's colours: update(vertices, colors=...) or update_from_volume() "
+                                 "of a volume that fuses colour")
+            pho = dict(photo=photo, colors=self.source_colors, color_image=target_frame_data["im"][:3])
         depth = torch.as_tensor(np.ascontiguousarray(target_frame_data["im"][-1], np.float32), device=self.device)
         self.tgt_pcd, self.pix_2_pcd = depth_2_pc_device(depth, self.intrinsics)
         P = self.source_pcd.shape[0]
@@ -574,7 +596,7 @@ class Registration:
                                 self.source_pcd, nrm, self.point_anchors, self.anchor_weight, None, depth,
                                 self._intr4(), self.prev_rot, self.prev_trans, complete_node_motion_data, icp_iters,
                                 rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None),
-                                depth_filter=depth_filter, **occ, **assoc)
+                                depth_filter=depth_filter, **pho, **occ, **assoc)
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)

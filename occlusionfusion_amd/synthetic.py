@@ -54,7 +54,10 @@ def _axis_angle(axis, theta):
 class SphereScene:
     """motion="nonrigid" (BASELINE configs 3-5): the sphere breathes and drifts, the plane is static.
     motion="rigid" (config 2): sphere + plane move as one rigid body about the sphere centre, at most
-    1.5° of rotation and 1 cm of translation per frame (≤2°, ≤1 cm)."""
+    1.5° of rotation and 1 cm of translation per frame (≤2°, ≤1 cm).
+    motion="spin": the sphere neither breathes nor drifts, it spins about spin_axis through its own centre by
+    spin_rate·t; the plane is static. Every frame's depth is frame 0's (with the frame's own noise): motion that depth
+    alone cannot see."""
     center: tuple = (0.0, 0.0, 1.4)
     radius: float = 0.35
     plane_z: float = 1.75
@@ -64,6 +67,8 @@ class SphereScene:
     occ_half: float = 0.07
     motion: str = "nonrigid"
     phase: float = 0.0          # time offset of the non-rigid motion and the occluder sweep (independent scenes)
+    spin_rate: float = math.radians(1.5)   # motion="spin": radians per frame about spin_axis through the centre
+    spin_axis: tuple = (0.3, 1.0, 0.2)
 
     @staticmethod
     def variant(seed):
@@ -93,6 +98,8 @@ class SphereScene:
         c = np.array(self.center, np.float64)
         if self.motion == "rigid":
             return c + self.rigid_pose(t)[1], self.radius
+        if self.motion == "spin":
+            return c, self.radius
         s = t + self.phase
         c = c + np.array([0.01 * math.sin(0.3 * s), 0.008 * math.sin(0.2 * s + 1.0), 0.012 * math.sin(0.25 * s)])
         r = self.radius * (1.0 + 0.03 * math.sin(0.35 * s))
@@ -109,7 +116,27 @@ class SphereScene:
         c, r = self.frame_params(t)
         out = pts.copy()
         on_sphere = pts[:, 2] < self.plane_z - 0.02
+        if self.motion == "spin":
+            out[on_sphere] = (pts[on_sphere] - c0) @ _axis_angle(self.spin_axis, self.spin_rate * t).T + c0
+            return out
         out[on_sphere] = c + (r / r0) * (pts[on_sphere] - c0)
+        return out
+
+    def undeform_points(self, pts_t, t):
+        """The closed-form inverse of deform_points: frame-t surface points back to canonical (frame-0) ones."""
+        pts = np.asarray(pts_t, np.float64)
+        c0 = np.array(self.center, np.float64)
+        if self.motion == "rigid":
+            R, T = self.rigid_pose(t)
+            return (pts - c0 - T) @ R + c0
+        c0, r0 = self.frame_params(0)
+        c, r = self.frame_params(t)
+        out = pts.copy()
+        on_sphere = pts[:, 2] < self.plane_z - 0.02
+        if self.motion == "spin":
+            out[on_sphere] = (pts[on_sphere] - c0) @ _axis_angle(self.spin_axis, self.spin_rate * t) + c0
+            return out
+        out[on_sphere] = c0 + (r0 / r) * (pts[on_sphere] - c)
         return out
 
     def render(self, cam, t=0, rng=None, noise=0.001):
@@ -187,6 +214,46 @@ def make_image(depth, rgb=None):
     im[:3] = rgb
     im[5] = depth
     return im
+
+
+# wave vectors (rad/m) and phases of surface_texture: three per channel, wavelengths 8.5 .. 13 cm, directions spread
+_TEX_K = 2.0 * math.pi * np.array([
+    [[9.1, 2.3, 1.1], [-2.9, 8.2, 3.7], [4.1, -5.3, 6.9]],
+    [[1.7, 10.3, -2.1], [7.7, -3.1, 4.3], [-5.9, 4.7, 7.1]],
+    [[3.3, 1.9, 9.7], [-8.3, -2.7, 3.1], [5.3, 7.9, -2.3]]])
+_TEX_PHI = np.array([[0.3, 1.7, 4.1], [2.9, 0.7, 5.3], [1.1, 3.7, 0.2]])
+
+
+def surface_texture(p):
+    """A smooth rgb texture attached to canonical positions p (P,3) -> (P,3) f64 in [0.05, 0.95]: per channel 0.5 plus
+    three incommensurate sinusoids of amplitude 0.15 and wavelengths of 8.5 to 13 cm."""
+    p = np.asarray(p, np.float64).reshape(-1, 3)
+    ph = np.einsum("cki,pi->pck", _TEX_K, p) + _TEX_PHI
+    return 0.5 + 0.15 * np.sin(ph).sum(-1)
+
+
+def textured_frame(scene, cam, seed, t, color_noise=0.01):
+    """(6,H,W) f32 image of frame t of the seeded sequence whose rgb is surface_texture of each pixel's canonical point
+    (the noise-free depth backprojected and taken back to frame 0 by scene.undeform_points) plus N(0, color_noise) per
+    channel, as an 8-bit image (multiples of 1/255); mid-grey where there is no surface, and on the occluder, which
+    has no canonical point. The depth plane is frame_depth's (its own noise stream)."""
+    depth = frame_depth(scene, cam, seed, t)
+    clean = scene.render(cam, t, None, 0.0)
+    H, W = clean.shape
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    z = clean.astype(np.float64)
+    surf = z > 0
+    if scene.occluder:
+        surf &= ~((np.abs((u - cam.cx) / cam.fx * scene.occ_z - scene.occluder_x(t)) <= scene.occ_half)
+                  & (np.abs(z - scene.occ_z) < 1e-3))
+    pts = np.stack([(u[surf] - cam.cx) * z[surf] / cam.fx, (v[surf] - cam.cy) * z[surf] / cam.fy, z[surf]], 1)
+    rgb = np.full((3, H, W), 0.5)
+    c = surface_texture(scene.undeform_points(pts, t))
+    if color_noise > 0:
+        c = c + np.random.default_rng(seed * 1000 + t + 500000).normal(0.0, color_noise, c.shape)
+    rgb[:, surf] = c.T
+    rgb = np.round(np.clip(rgb, 0.0, 1.0) * 255.0) / 255.0
+    return make_image(depth, rgb.astype(np.float32))
 
 
 def sample_nodes(points, coverage, seed=0):

@@ -288,6 +288,27 @@ class TSDFVolume:
         call("ofx_volume_to_dense", byref(self.desc), ptr(t), ptr(out), stream_ptr())
         return out
 
+    def voxel_rgb(self, voxel_ids):
+        """The fused colour of voxels given by their C-order ids (as WarpField.surface_points' "voxel" column; whole
+        volumes only) -> (P,3) f32 rgb in [0,1] on the device: id -> brick slot -> packed colour c -> b = floor(c /
+        65536), g = floor((c - 65536 b) / 256), r = the rest, each divided by 255 (ofx_pack_color's inverse for 8-bit
+        colours). An id outside the volume (the padding rows' -1) gives zeros. Torch integer math on torch's current
+        stream, no host read; off the hot path."""
+        if self.brick_x0 != 0 or self.n_slots != int(np.prod((self._vol_dim + 7) // 8)) * 512:
+            raise ValueError("voxel_rgb needs a whole volume, not a shard")
+        ids = voxel_ids if isinstance(voxel_ids, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(voxel_ids))
+        ids = ids.to(device=self.device, dtype=torch.int64).reshape(-1)
+        Dx, Dy, Dz = (int(x) for x in self._vol_dim)
+        nby, nbz = (Dy + 7) // 8, (Dz + 7) // 8
+        ok = (ids >= 0) & (ids < Dx * Dy * Dz)
+        t = torch.where(ok, ids, torch.zeros_like(ids))
+        k, r = t % Dz, t // Dz
+        j, i = r % Dy, r // Dy
+        slot = (((i // 8) * nby + j // 8) * nbz + k // 8) * 512 + ((i % 8) * 8 + j % 8) * 8 + k % 8
+        c = self.color_b[slot].to(torch.int64)   # packed colours are integers below 2^24: exact in f32
+        rgb = torch.stack([c % 256, (c // 256) % 256, c // 65536], 1).to(torch.float32) / 255.0
+        return torch.where(ok[:, None], rgb, torch.zeros_like(rgb))
+
     def get_volume_device(self):
         """(tsdf, color, weight) C-order device tensors of this shard (x-slab [x_lo, x_hi))."""
         return self._dense(self.tsdf_b), self._dense(self.color_b), self._dense(self.weight_b)

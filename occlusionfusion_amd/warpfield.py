@@ -466,6 +466,8 @@ class WarpField:
         associate takes as they are — and "count" is the device int32[2] = [accepted, emitted]. The arrays belong to
         the warp field's sampler: the next call with the same max_points overwrites them.
 
+        surface_colors(the result) adds the points' fused colours.
+
         Raises if no skin cache has been built (skin_tsdf_cache()), or for a sharded volume."""
         from .surface import CODE_NAMES, SurfaceSampler
         if self._cache is None:
@@ -488,6 +490,13 @@ class WarpField:
         if with_codes:
             res["histogram"] = [int(x) for x in host[2:2 + len(CODE_NAMES)]]
         return res
+
+    def surface_colors(self, model):
+        """Add "colors" to a surface_points result (sliced or padded): the points' fused rgb in [0,1], f32 (.,3)
+        (TSDFVolume.voxel_rgb of "voxel"; zeros in the padding rows) — what ProjectiveAssociator.associate_photo matches
+        the live frame's colours against. Torch math on the current stream, no host read. -> the colours."""
+        model["colors"] = self.tsdf.voxel_rgb(model["voxel"])
+        return model["colors"]
 
     def _skin_plan(self, nodes, n_old, n_added):
         """Enqueue ofx_skin_grow_plan for nodes [n_old, n_old + n_added) (n_added: device int32) against the current
