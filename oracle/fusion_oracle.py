@@ -799,9 +799,13 @@ def gn_arap(graph_nodes, source_node_position, target_node_position, valid_nodes
 
 def gn_system(graph_nodes, graph_edges, target_node_position, node_confidence, source_points, anchors,
               weights, target_points, intrinsics, R, t, lm_factor=1e-7, include_data=True, include_reg=True,
-              **params):
+              graph_edges_weights=None, target_px=None, target_py=None, **params):
     """A, b, ||res|| of one GN linearisation at (R, t) — dense, for block-level and sharding tests.
-    include_data / include_reg select the data rows / the ARAP+motion rows (a match shard's share)."""
+    include_data / include_reg select the data rows / the ARAP+motion rows (a match shard's share).
+    lambda_flow (with target_px / target_py, zeros by default) and use_edge_weighting (with graph_edges_weights) are
+    read from params and give gn_optimize's entries, the flow-rotation precedence quirk included (model.py:505-510);
+    without them the result is bit for bit the default one. loss2_data / loss2_arap / loss2_motion are the three
+    shares of loss2 (0 for rows left out)."""
     out = {}
     p = dict(GN_DEFAULTS)
     p.update(params)
@@ -821,41 +825,64 @@ def gn_system(graph_nodes, graph_edges, target_node_position, node_confidence, s
     R = np.asarray(R, F64)
     t = np.asarray(t, F64)
     ld, la, lmo = math.sqrt(p['lambda_depth']), math.sqrt(p['lambda_arap']), math.sqrt(p['lambda_motion'])
+    lf = math.sqrt(p['lambda_flow'])
     defp = np.zeros((M, 3))
     for k in range(4):
         nk = anc[:, k]
         defp += wts[:, k:k + 1] * (np.einsum('mij,mj->mi', R[nk], src - g[nk]) + g[nk] + t[nk])
     zinv = 1.0 / (defp[:, 2] + 1e-7)
-    mfx = -(fx * defp[:, 0] * zinv) * zinv
-    mfy = -(fy * defp[:, 1] * zinv) * zinv
+    fx_div_z, fy_div_z = fx * zinv, fy * zinv
+    fx_mul_x_div_z, fy_mul_y_div_z = (fx * defp[:, 0]) * zinv, (fy * defp[:, 1]) * zinv
+    mfx = -fx_mul_x_div_z * zinv
+    mfy = -fy_mul_y_div_z * zinv
     rowsM = np.arange(M) * 3
     J = np.zeros((M * 3, N * 6))
     for k in range(4):
         nk = anc[:, k]
         wk = wts[:, k]
         S = -skew(wk[:, None] * np.einsum('mij,mj->mi', R[nk], src - g[nk]))
+        if lf != 0.0:   # flow translation columns, ahead of the depth ones as in gn_optimize
+            J[rowsM, 3 * N + 3 * nk + 0] += lf * wk * fx_div_z
+            J[rowsM, 3 * N + 3 * nk + 2] += lf * wk * mfx
+            J[rowsM + 1, 3 * N + 3 * nk + 1] += lf * wk * fy_div_z
+            J[rowsM + 1, 3 * N + 3 * nk + 2] += lf * wk * mfy
         for c in range(3):
             J[rowsM + c, 3 * N + 3 * nk + c] += ld * wk
         for j in range(3):
-            J[rowsM, 3 * nk + j] += mfx * S[:, 2, j]
-            J[rowsM + 1, 3 * nk + j] += mfy * S[:, 2, j]
+            if lf != 0.0:   # the reference's precedence quirk: mfx·S[2,j] is not multiplied by lf
+                J[rowsM, 3 * nk + j] += lf * fx_div_z * S[:, 0, j] + mfx * S[:, 2, j]
+                J[rowsM + 1, 3 * nk + j] += lf * fy_div_z * S[:, 1, j] + mfy * S[:, 2, j]
+            else:
+                J[rowsM, 3 * nk + j] += mfx * S[:, 2, j]
+                J[rowsM + 1, 3 * nk + j] += mfy * S[:, 2, j]
         for i in range(3):
             for j in range(3):
                 J[rowsM + i, 3 * nk + j] += ld * S[:, i, j]
     rd = (ld * (defp - tgt)).reshape(-1)
-    edges, _ = gn_edges(graph_edges)
+    if lf != 0.0:
+        tpx = np.zeros(M) if target_px is None else np.asarray(target_px, F64).reshape(-1)
+        tpy = np.zeros(M) if target_py is None else np.asarray(target_py, F64).reshape(-1)
+        rd[rowsM] += lf * (fx_mul_x_div_z + cx - tpx)
+        rd[rowsM + 1] += lf * (fy_mul_y_div_z + cy - tpy)
+    edges, (ei, ek) = gn_edges(graph_edges)
     E = edges.shape[0] if include_reg else 0
     Js, rs = ([J], [rd]) if include_data else ([], [])
+    l2 = dict(data=float(rd @ rd) if include_data else 0.0, arap=0.0, motion=0.0)
     if E:
+        ew = np.ones(E)
+        if p['use_edge_weighting']:
+            ew = float(np.asarray(graph_edges).shape[1]) * np.asarray(graph_edges_weights, F64)[ei, ek]
         i0, i1 = edges[:, 0], edges[:, 1]
         delta = np.einsum('eij,ej->ei', R[i0], g[i1] - g[i0])
-        rs.append((la * (delta + g[i0] + t[i0] - (g[i1] + t[i1]))).reshape(-1))
+        ra = (la * ew[:, None] * (delta + g[i0] + t[i0] - (g[i1] + t[i1]))).reshape(-1)
+        rs.append(ra)
+        l2['arap'] = float(ra @ ra)
         Ja = np.zeros((E * 3, N * 6))
         rowsE = np.arange(E) * 3
         for c in range(3):
-            Ja[rowsE + c, 3 * N + 3 * i0 + c] += la
-            Ja[rowsE + c, 3 * N + 3 * i1 + c] += -la
-        Sa = -la * skew(delta)
+            Ja[rowsE + c, 3 * N + 3 * i0 + c] += la * ew
+            Ja[rowsE + c, 3 * N + 3 * i1 + c] += -la * ew
+        Sa = -la * ew[:, None, None] * skew(delta)
         for i in range(3):
             for j in range(3):
                 Ja[rowsE + i, 3 * i0 + j] += Sa[:, i, j]
@@ -866,7 +893,9 @@ def gn_system(graph_nodes, graph_edges, target_node_position, node_confidence, s
         for c in range(3):
             Jm[ids * 3 + c, 3 * N + 3 * ids + c] += lmo * conf
         Js.append(Jm)
-        rs.append((lmo * conf[:, None] * (t + g - tpos)).reshape(-1))
+        rm = (lmo * conf[:, None] * (t + g - tpos)).reshape(-1)
+        rs.append(rm)
+        l2['motion'] = float(rm @ rm)
     if not Js:
         Js, rs = [np.zeros((0, 6 * N))], [np.zeros(0)]
     Jall = np.concatenate(Js, 0)
@@ -875,6 +904,7 @@ def gn_system(graph_nodes, graph_edges, target_node_position, node_confidence, s
     out['b'] = -(Jall.T @ res)
     out['loss'] = float(np.linalg.norm(res))
     out['loss2'] = float(res @ res)
+    out['loss2_data'], out['loss2_arap'], out['loss2_motion'] = l2['data'], l2['arap'], l2['motion']
     return out
 
 
