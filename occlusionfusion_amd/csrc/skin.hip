@@ -202,6 +202,11 @@ __global__ __launch_bounds__(256) void k_skin_volume(BrickGeom g, const float* _
     int ids[4];
     float w[4];
     finish_skin(tk[h], K, cutoff, denom, ids, w);
+    // a lane past the volume's end (a clipped brick) is no voxel: no anchors, so that it stays out of the brick's palette
+    if (i0 + (l >> 6) >= g.Dx || j0 + ((l >> 3) & 7) >= g.Dy || k0 + (l & 7) >= g.Dz) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { ids[s] = -1; w[s] = 0.f; }
+    }
     ushort4 a;
     a.x = ids[0] < 0 ? kNoAnchor : (uint16_t)ids[0];
     a.y = ids[1] < 0 ? kNoAnchor : (uint16_t)ids[1];

@@ -1,8 +1,11 @@
-"""GPU: the certified fast arithmetic of the integrate kernels (f32 pixel rounding with an f64 fallback near
-ties, cheap SDF rounding certificate) against the numpy oracle on ADVERSARIAL points, bit for bit:
+"""GPU: the certified fast arithmetic that the integrate kernels share (the device functions pixel_of: f32 pixel
+rounding with an f64 fallback near ties, and sdf_color_update: cheap SDF rounding certificate) against the numpy oracle
+on ADVERSARIAL points, bit for bit:
 projections within 1e-12 .. 3e-4 px of a half-integer rounding tie, the image border (-0.5, W-0.5, the
 -0 -> 0 case), subnormal / tiny / zero / negative / non-finite depths, and random old tsdf / weight / colour
-with depths around the truncation band. Runs through ofx_integrate_points (TSDFVolume.integrate_points)."""
+with depths around the truncation band. Runs through ofx_integrate_points (TSDFVolume.integrate_points) only, at obs_weight 1: the bricked
+kernels themselves (k_integrate_pal4, k_integrate<...>, k_integrate_src) and obs_weight != 1 are the matter of
+tests/test_gpu_skin_cache_edges.py."""
 import numpy as np
 import pytest
 import torch
