@@ -902,6 +902,32 @@ int ofx_gn_prefetch_stats(void* handle, int64_t* used, int64_t* missed);
  * back the next solve's first launches. (Round 6; no ABI struct changes.) */
 int ofx_gn_set_idle_hook(void* handle, void (*fn)(void*), void* arg);
 
+/* Per-match weights and a robust kernel (M-estimator, IRLS) on the data rows of OFX_GN_OPTIMIZE: match m's residual
+ * triple and Jacobian rows are multiplied by s_m = match_weights[m] · s_rob(e_m), with e_m = |p_m - tgt_m| the match's
+ * geometric distance in metres at the current linearisation (independent of the lambdas and of the flow rows):
+ *   OFX_ROBUST_NONE   s_rob = 1
+ *   OFX_ROBUST_HUBER  s_rob = 1 for e <= scale, sqrt(scale / e) beyond
+ *   OFX_ROBUST_TUKEY  s_rob = 1 - (e / scale)² for e < scale, 0 beyond (the square root of the biweight)
+ * s is recomputed at every GN step. The ARAP and motion rows, the OFX_GN_ARAP mode and matches outside the [m0, m1) of
+ * ofx_gn_linearize are untouched. (ABI 5: a new struct and a new entry point, no existing struct changes.) */
+enum { OFX_ROBUST_NONE = 0, OFX_ROBUST_HUBER = 1, OFX_ROBUST_TUKEY = 2 };
+typedef struct ofx_gn_robust {
+  const float* match_weights;  /* (M) device, or NULL = all 1. Multiplies match m's residual and Jacobian rows, as
+                                  correspondence_weights does in DeformNet.forward (model/model.py:1338,1374-1378;
+                                  objective weight = its square). The sign is immaterial; a non-finite weight makes
+                                  the solve invalid */
+  int32_t kernel;              /* OFX_ROBUST_NONE 0 / OFX_ROBUST_HUBER 1 / OFX_ROBUST_TUKEY 2 */
+  int32_t _pad;
+  double scale;                /* metres, > 0 when kernel != NONE: Huber delta / Tukey c */
+} ofx_gn_robust;
+/* Sticky on the handle until replaced or cleared (r = NULL, or no weights and OFX_ROBUST_NONE: off, the solver as it
+ * is without this call). The next ofx_gn_setup / ofx_gn_solve / ofx_gn_prepare[_after] on the handle copies
+ * match_weights into an array of the handle's (stream-ordered, with the problem's upload); the pointer is not read
+ * after that setup. A prefetched setup is used by ofx_gn_solve only if it was prepared under the handle's current
+ * setting (same pointer, kernel and scale); otherwise it counts as missed and the setup runs inline. An unknown kernel,
+ * or a kernel with a scale that is not finite and > 0, is refused (OFX_ERR_ARG); device values are not checked. */
+int ofx_gn_set_robust(void* handle, const ofx_gn_robust* r);
+
 #ifdef __cplusplus
 }
 #endif

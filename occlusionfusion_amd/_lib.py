@@ -79,6 +79,13 @@ class GnResult(ctypes.Structure):
     _fields_ = [("rot", P), ("trans", P), ("status", P), ("loss_log", P)]
 
 
+class GnRobust(ctypes.Structure):
+    _fields_ = [("match_weights", P), ("kernel", c_int32), ("_pad", c_int32), ("scale", c_double)]
+
+
+ROBUST_KERNELS = {"none": 0, "huber": 1, "tukey": 2}   # OFX_ROBUST_* (include/ofx.h)
+
+
 _SIGS = {
     "ofx_abi_version": [],
     "ofx_volume_num_slots": [P, P],
@@ -175,6 +182,7 @@ _SIGS = {
     "ofx_gn_prefetch_stats": [P, P, P],
     "ofx_gn_share_history": [P, P],
     "ofx_gn_set_idle_hook": [P, P, P],
+    "ofx_gn_set_robust": [P, P],
 }
 
 

@@ -315,7 +315,7 @@ def photo_params(photo):
 def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
               valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3,
               rigid_iters=0, rigid=None, occlusion=False, renderer=None, splat_radius=None, occl_margin=0.01,
-              depth_filter=None, photo=None, colors=None, color_image=None, **assoc):
+              depth_filter=None, photo=None, colors=None, color_image=None, robust=None, **assoc):
     """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
     associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
     matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
@@ -349,7 +349,14 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     (3,H,W), both rgb in [0,1] (a ValueError without them, before any device work). The frame's normal map comes from
     prepare_depth_device with the association's edge_max: radius 0 without depth_filter (its vertex map is then the raw
     one bit for bit), the filter's settings with it. `mode` is ignored under photo: the target is always the vertex.
-    The rigid stage and the occlusion gate work as before."""
+    The rigid stage and the occlusion gate work as before.
+
+    robust: None — the loop as it was; "huber", "tukey" or a dict of kernel / scale (registration.ROBUST_DEFAULTS; another
+    key is a TypeError, an unknown kernel a ValueError, before any device work) — forwarded to every solver.optimize of
+    the loop: an M-estimator on the data rows, so a match just inside dist_max no longer pulls like a perfect one."""
+    from .registration import robust_params
+    robust_params(robust)
+    rob = {} if robust is None else {"robust": robust}
     from .image_proc import PREPARE_DEFAULTS, backproject_depth_device, prepare_depth_device
     rigid_iters = int(rigid_iters)
     if rigid_iters < 0:
@@ -435,7 +442,7 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
             raise TooFewMatches(f"projective association {it} emitted {m['emitted']} matches of {m['accepted']} accepted "
                                 f"({dict(zip(PHOTO_CODE_NAMES, m['histogram']))}); at least 16 (4·K) are needed to solve")
         out = solver.optimize(graph_nodes, graph_edges, graph_edges_weights, tloc, tconf, m["src"], m["anchors"],
-                              m["weights"], m["tgt"], (fx, fy, cx, cy), prev_rot=rot, prev_trans=trans)
+                              m["weights"], m["tgt"], (fx, fy, cx, cy), prev_rot=rot, prev_trans=trans, **rob)
         rot, trans = out["node_rotations"], out["node_translations"]
     if rig is not None:
         out["rigid"] = rig

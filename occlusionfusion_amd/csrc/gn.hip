@@ -26,6 +26,8 @@ struct Upload {
   int use_ew;
   int old_N;
   int64_t old_nnzb, n;
+  const float* mw;   // per-match weights (ofx_gn_set_robust) or null = all 1, into mw_dst (null: the setting is off)
+  double* mw_dst;
 };
 // caller node -> row (negative ids stay negative)
 __device__ __forceinline__ int to_row(const GnDev& g, int a) { return a >= 0 ? g.iperm[a] : a; }
@@ -54,6 +56,7 @@ __global__ __launch_bounds__(256) void k_upload(GnDev g, Upload u) {
   if (i < 3 * (int64_t)M) { g.src[i] = u.src[i]; g.tgt[i] = u.tgt[i]; }
   if (i < 4 * (int64_t)M) { g.wts[i] = u.wts[i]; g.anc[i] = to_row(g, u.anc[i]); }
   if (i < M) { g.tpx[i] = u.tpx ? (double)u.tpx[i] : 0.0; g.tpy[i] = u.tpy ? (double)u.tpy[i] : 0.0; }
+  if (u.mw_dst && i < M) u.mw_dst[i] = u.mw ? (double)u.mw[i] : 1.0;
   if (i < (int64_t)N * NB) {
     const int r = (int)(i / NB), k = (int)(i % NB);
     const int p = g.perm[r];
@@ -3616,7 +3619,7 @@ __global__ void k_finish(GnDev g, float* __restrict__ rot, float* __restrict__ t
 
 // --------------------------------------------------------------------------------------------
 static void free_all(Gn* g) {
-  void* ptrs[] = {g->nodes, g->tpos, g->conf, g->src, g->wts, g->tgt, g->tpx, g->tpy, g->ew, g->anc, g->edges,
+  void* ptrs[] = {g->nodes, g->tpos, g->conf, g->src, g->wts, g->tgt, g->tpx, g->tpy, g->mw, g->ew, g->anc, g->edges,
                   g->term_node, g->J, g->res, g->map, g->row_ptr, g->col, g->blk_row, g->row_cnt, g->wl, g->Aw, g->stopw, g->blk_off, g->blk_cnt,
                   g->blk_list, g->blk_tmp, g->node_tmp, g->node_off, g->node_cnt, g->node_list, g->blk_first, g->node_first, g->R, g->t, g->A_own, g->rhs_own, g->Mcl,
                   g->st, g->m0, g->m1, g->pcs, g->racc,
@@ -4056,6 +4059,11 @@ static bool same_problem(const ofx_gn_problem& a, const ofx_gn_problem& b) {   /
          a.target_py == b.target_py && a.fx == b.fx && a.fy == b.fy && a.cx == b.cx && a.cy == b.cy;
 }
 
+static bool same_robust(const ofx_gn_robust& a, const ofx_gn_robust& b) {
+  return a.match_weights == b.match_weights && a.kernel == b.kernel &&
+         (a.kernel == OFX_ROBUST_NONE || a.scale == b.scale);
+}
+
 static bool same_params(const ofx_gn_params& a, const ofx_gn_params& b) {
   return a.num_iter == b.num_iter && a.use_edge_weighting == b.use_edge_weighting &&
          a.pcg_max_iter == b.pcg_max_iter && a.pcg_warm == b.pcg_warm && a.lambda_flow == b.lambda_flow &&
@@ -4101,6 +4109,7 @@ int ofx_gn_create(int32_t max_nodes, int32_t max_matches, void** handle) {
   if (hipMalloc((void**)&(ptr), (size_t)(n) * sizeof(*(ptr))) != hipSuccess) { free_all(g); delete g; set_error("hipMalloc failed"); return OFX_ERR_ALLOC; }
   ALLOC(g->nodes, 3 * N); ALLOC(g->tpos, 3 * N); ALLOC(g->conf, N);
   ALLOC(g->src, 3 * M); ALLOC(g->wts, 4 * M); ALLOC(g->tgt, 3 * M); ALLOC(g->tpx, M); ALLOC(g->tpy, M);
+  ALLOC(g->mw, M);
   ALLOC(g->anc, 4 * M);
   ALLOC(g->map, N * N); ALLOC(g->row_ptr, N + 1); ALLOC(g->row_cnt, N + 2);
   ALLOC(g->node_off, N + 1); ALLOC(g->node_cnt, N + 1); ALLOC(g->node_first, N * 128);
@@ -4345,6 +4354,7 @@ int ofx_gn_setup(void* handle, const ofx_gn_problem* pb, const ofx_gn_params* pr
   g->prep_status = OFX_OK;
   const int fs = fence_side(g, as_stream(s));   // its side-stream kernels write the buffers this setup reuses
   if (fs) return fs;
+  g->rob_setup = g->rob;
   return gn_setup(g, pb, prm, nnz_blocks, s);
 }
 
@@ -4372,6 +4382,7 @@ static int prepare_impl(Gn* g, const ofx_gn_problem* pb, const ofx_gn_params* pr
   g->prep_pb.prev_rot = nullptr;    // the pose is loaded by the solve (k_pose)
   g->prep_pb.prev_trans = nullptr;
   g->prep_prm = *prm;
+  g->rob_setup = g->rob;   // (the worker is idle: prep_wait above) the prefetched setup is made under today's setting
   g->prepared = true;
   g->side_dirty = true;
   if (!g->worker.joinable()) g->worker = std::thread(prep_worker, g);
@@ -4416,6 +4427,25 @@ int ofx_gn_set_idle_hook(void* handle, void (*fn)(void*), void* arg) {
   OFX_CHECK_ARG(g, "null handle");
   g->idle_fn = fn;
   g->idle_arg = fn ? arg : nullptr;
+  return OFX_OK;
+}
+
+int ofx_gn_set_robust(void* handle, const ofx_gn_robust* r) {
+  Gn* g = (Gn*)handle;
+  ofx_gn_robust v{};   // NULL = off
+  if (r) {   // (the setting is checked before the handle is touched)
+    OFX_CHECK_ARG(r->kernel == OFX_ROBUST_NONE || r->kernel == OFX_ROBUST_HUBER || r->kernel == OFX_ROBUST_TUKEY,
+                  "unknown robust kernel %d (OFX_ROBUST_NONE 0, OFX_ROBUST_HUBER 1, OFX_ROBUST_TUKEY 2)", r->kernel);
+    OFX_CHECK_ARG(r->kernel == OFX_ROBUST_NONE || (std::isfinite(r->scale) && r->scale > 0.0),
+                  "robust scale must be finite and > 0 with a kernel set (got %g)", r->scale);
+    v.match_weights = r->match_weights;
+    v.kernel = r->kernel;
+    v.scale = r->kernel == OFX_ROBUST_NONE ? 0.0 : r->scale;
+  }
+  OFX_CHECK_ARG(g, "null handle");
+  // (only the caller's setting: a prefetch in flight keeps the one it was queued under, rob_setup, and the next solve
+  // compares the two)
+  g->rob = v;
   return OFX_OK;
 }
 
@@ -4594,6 +4624,11 @@ static int gn_setup(Gn* g, const ofx_gn_problem* pb, const ofx_gn_params* prm, i
   u.tgt = pb->tgt; u.tpx = pb->target_px; u.tpy = pb->target_py; u.ew = pb->edge_weights; u.prev_R = pb->prev_rot;
   u.prev_t = pb->prev_trans; u.anc = pb->anchors; u.edges = pb->edges; u.use_ew = prm->use_edge_weighting;
   u.old_N = g->pat_N; u.old_nnzb = g->pat_N > 0 ? g->pat_nnzb : 0;
+  // the setting this setup is made under (rob_setup: set by the entry point, on the caller's thread); no data rows in
+  // the arap mode, so nothing to weigh there
+  const bool rob = robust_on(g->rob_setup) && prm->mode == OFX_GN_OPTIMIZE;
+  u.mw = rob ? g->rob_setup.match_weights : nullptr;
+  u.mw_dst = rob ? g->mw : nullptr;
   {
     int64_t n = g->T;
     for (int64_t v : {9 * (int64_t)N, 4 * (int64_t)M, ne, u.old_nnzb, (int64_t)3 * kMaxLog, (int64_t)2 * (kMaxLog + 1),
@@ -4890,7 +4925,7 @@ int ofx_gn_solve(void* handle, const ofx_gn_problem* pb, const ofx_gn_params* pr
   // a setup prefetched for exactly this problem (ofx_gn_prepare): wait for it on the caller's stream and load
   // the pose; otherwise (none, another problem, or it failed) set up here
   const bool use = g->prepared && g->prep_status == OFX_OK && same_problem(g->prep_pb, *pb) &&
-                   same_params(g->prep_prm, *prm);
+                   same_params(g->prep_prm, *prm) && same_robust(g->rob_setup, g->rob);
   if (g->prepared) ++(use ? g->pf_used : g->pf_missed);
   g->prepared = false;
   g->prep_status = OFX_OK;
@@ -4905,6 +4940,7 @@ int ofx_gn_solve(void* handle, const ofx_gn_problem* pb, const ofx_gn_params* pr
                          pb->prev_trans);
     OFX_LAUNCH_CHECK();
   } else {
+    g->rob_setup = g->rob;
     st = gn_setup(g, pb, prm, nullptr, s);
     if (st) return st;
   }

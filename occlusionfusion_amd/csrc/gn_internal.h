@@ -273,6 +273,12 @@ struct Gn : GnDev {
   bool side_dirty = false;
   hipEvent_t ev_side = nullptr;
   int64_t pf_used = 0, pf_missed = 0;   // solves that used / discarded a prefetched setup
+  // per-match weights and robust data rows (ofx_gn_set_robust): rob is the caller's sticky setting; rob_setup the one
+  // the last (or the prefetched, in-flight) setup was made under, which k_terms<true> then runs with — its
+  // match_weights pointer is compared, never read again; mw holds the weights k_upload copied (max_matches doubles,
+  // all 1 without a pointer). Host-only: the kernels get mw through Upload / RobustArg, GnDev stays as it is.
+  ofx_gn_robust rob{}, rob_setup{};
+  double* mw = nullptr;
   int32_t ep_next = 1;
   int as_env = -1;                  // OFX_PRECOND override of params.precond (-1: none; 3: direct)
   // exact dense solve (OFX_PRECOND_DIRECT, OFX_GN_OPTIMIZE): the dense lower triangle (dn_n x dn_n, row-major) and b / x
@@ -299,6 +305,9 @@ struct Gn : GnDev {
   double prep_wait_us = 0.0;
 #endif
 };
+
+// a setting that changes the data rows (else k_terms<false>, the solver as it is without ofx_gn_set_robust)
+inline bool robust_on(const ofx_gn_robust& r) { return r.match_weights != nullptr || r.kernel != OFX_ROBUST_NONE; }
 
 // Order stream hs after everything the prefetch worker enqueued on the handle's side stream (call after
 // prep_wait: the worker has finished enqueuing). Every entry point that touches the handle's buffers on a

@@ -17,11 +17,40 @@ struct DataCoef {
 // operation for operation, so the assembled A and b are the same bits.
 // (kRec = 20: gn_internal.h)
 
-// slot k of data term m: its anchor's [v w]; slot 0 also the term's shared scalars
+// Per-match weights and the robust kernel of the data rows (ofx_gn_set_robust), k_terms<true>'s own argument: mw the
+// handle's copy of the weights (k_upload), c the Huber delta / Tukey c in metres, c2 = c² (Tukey's u = e² / c²)
+struct RobustArg {
+  const double* mw;
+  double c, c2;
+  int kernel;
+};
+// (k_terms' trailing argument pack holds exactly one RobustArg when kRobust, none otherwise)
+__device__ __forceinline__ const RobustArg& only(const RobustArg& rb) { return rb; }
+
+// The row scale of a match at geometric distance² e2 (metres²): mw · s_rob, with s_rob the square root of the IRLS weight
+// ρ'(e)/e — Huber: 1 up to delta, sqrt(delta / e) beyond; Tukey: 1 - u below u = e²/c² = 1 (the root of the biweight
+// (1 - u)², no sqrt), 0 from there on. A NaN distance gives NaN (Huber) or a zero scale on a NaN residual (Tukey): either
+// way the term's loss partial is not finite and the solve is flagged.
+__device__ __forceinline__ double robust_scale(const RobustArg& rb, double mw, double e2) {
+  double s = 1.0;
+  if (rb.kernel == OFX_ROBUST_TUKEY) {
+    const double u = e2 / rb.c2;
+    s = u < 1.0 ? 1.0 - u : 0.0;
+  } else if (rb.kernel == OFX_ROBUST_HUBER) {
+    const double e = sqrt(e2);
+    s = e <= rb.c ? 1.0 : sqrt(rb.c / e);
+  }
+  return mw * s;
+}
+
+// slot k of data term m: its anchor's [v w]; slot 0 also the term's shared scalars. kRobust: w is w_k · s, the match's row
+// scale (the blocks are linear in w_k: term_block then gives s times the unscaled rows; the tail scalars are not scaled)
+template <bool kRobust>
 __device__ __forceinline__ void data_record(const GnDev& g, const DataCoef& dc, int64_t m, int k, const double p[3],
-                                            double zinv, double* __restrict__ rec) {
+                                            double zinv, double* __restrict__ rec, double s) {
   int a = g.anc[m * 4 + k];
   double w = g.wts[m * 4 + k];
+  if (kRobust) w = w * s;
   const double* R = g.R + 9 * (int64_t)a;
   const double* gn = g.nodes + 3 * (int64_t)a;
   double d0 = g.src[3 * m] - gn[0], d1 = g.src[3 * m + 1] - gn[1], d2 = g.src[3 * m + 2] - gn[2];
@@ -99,13 +128,21 @@ __device__ __forceinline__ void anchor_term(const GnDev& g, int64_t m, int k, do
 // (kRec above); slot 0 also writes the residual triple and the loss partials. Terms outside this rank's
 // share (data matches outside [m0,m1), regularisers when !add_reg) get all-zero records (exact zero
 // blocks) so the fixed contribution lists stay valid.
-__global__ __launch_bounds__(kBlk) void k_terms(GnDev g, DataCoef dc, int m0, int m1, int add_reg) {
+// kRobust = false is the kernel without ofx_gn_set_robust (Rb empty: its arguments and code are what they were);
+// kRobust = true takes one RobustArg more and scales each data term in [m0, m1) by s = mw[t] · s_rob(|p - tgt|),
+// recomputed per linearisation (IRLS): w_k -> w_k · s in the record, r -> r · s, the loss partial from the scaled r.
+// s = 0 zeroes every [v w] word of the record: exact zero blocks, which the contribution lists tolerate as they do a
+// foreign match's.
+template <bool kRobust, typename... Rb>
+__global__ __launch_bounds__(kBlk) void k_terms(GnDev g, DataCoef dc, int m0, int m1, int add_reg, Rb... rb) {
   // every kernel-argument field in SGPRs up front, in one scalar trip (left to the compiler, each branch loaded its own
   // fields after the branch: four dependent scalar trips ahead of the first vector load)
   asm volatile("" :: "s"(g.J), "s"(g.anc), "s"(g.wts), "s"(g.R), "s"(g.nodes), "s"(g.src), "s"(g.t), "s"(g.tgt),
                "s"(g.tpx), "s"(g.tpy), "s"(g.edges), "s"(g.ew), "s"(g.res), "s"(g.T), "s"(g.M), "s"(g.N), "s"(g.NB),
                "s"(g.conf), "s"(g.tpos), "s"(g.prm.mode), "s"(g.part_loss), "s"(m0), "s"(m1), "s"(add_reg));
   asm volatile("" :: "s"(dc.lf), "s"(dc.ld), "s"(dc.la), "s"(dc.lm), "s"(dc.fx), "s"(dc.fy), "s"(dc.cx), "s"(dc.cy));
+  if constexpr (kRobust)
+    asm volatile("" :: "s"(only(rb...).mw), "s"(only(rb...).c), "s"(only(rb...).c2), "s"(only(rb...).kernel));
   const int64_t id = blockIdx.x * (int64_t)kBlk + threadIdx.x;
   const int64_t t = id >> 2;
   const int k = (int)(id & 3);
@@ -122,6 +159,8 @@ __global__ __launch_bounds__(kBlk) void k_terms(GnDev g, DataCoef dc, int m0, in
         // the residual's target values are loaded by every slot up front (no trip behind the k == 0 branch)
         const double tpx = g.tpx[t], tpy = g.tpy[t];
         const double tg0 = g.tgt[3 * t], tg1 = g.tgt[3 * t + 1], tg2 = g.tgt[3 * t + 2];
+        double mwt = 1.0;   // (kRobust) the match's weight, by every slot with the targets: each slot scales its own words
+        if constexpr (kRobust) mwt = only(rb...).mw[t];
         double c[3];
         anchor_term(g, t, k, c);
         const int base = (int)(threadIdx.x & 63) & ~3;
@@ -131,11 +170,17 @@ __global__ __launch_bounds__(kBlk) void k_terms(GnDev g, DataCoef dc, int m0, in
 #pragma unroll
           for (int d = 0; d < 3; ++d) p[d] += __shfl(c[d], base + kk, 64);
         double zinv = 1.0 / (p[2] + 1e-7);
-        data_record(g, dc, t, k, p, zinv, rec);
+        double s = 1.0;
+        if constexpr (kRobust) {
+          const double e0 = p[0] - tg0, e1 = p[1] - tg1, e2 = p[2] - tg2;
+          s = robust_scale(only(rb...), mwt, e0 * e0 + e1 * e1 + e2 * e2);
+        }
+        data_record<kRobust>(g, dc, t, k, p, zinv, rec, s);
         if (k == 0) {
           r[0] = dc.lf * (dc.fx * p[0] * zinv + dc.cx - tpx) + dc.ld * (p[0] - tg0);
           r[1] = dc.lf * (dc.fy * p[1] * zinv + dc.cy - tpy) + dc.ld * (p[1] - tg1);
           r[2] = dc.ld * (p[2] - tg2);
+          if constexpr (kRobust) { r[0] *= s; r[1] *= s; r[2] *= s; }
           l2[0] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
         }
       } else {
@@ -420,7 +465,17 @@ int gn_linearize(Gn* g, int gn_iter, int m0, int m1, int add_reg, double* A, dou
   dc.lf = sqrt(g->prm.lambda_flow); dc.ld = sqrt(g->prm.lambda_depth);
   dc.la = sqrt(g->prm.lambda_arap); dc.lm = sqrt(g->prm.lambda_motion);
   dc.fx = g->fx; dc.fy = g->fy; dc.cx = g->cx; dc.cy = g->cy;
-  hipLaunchKernelGGL(k_terms, dim3(g->nwg_terms), dim3(kBlk), 0, hs, *g, dc, m0, m1, add_reg);
+  const ofx_gn_robust& rs = g->rob_setup;   // the setting the setup was made under (its weights are in g->mw)
+  if (robust_on(rs) && g->prm.mode == OFX_GN_OPTIMIZE) {
+    RobustArg rb;
+    rb.mw = g->mw;
+    rb.kernel = rs.kernel;
+    rb.c = rs.kernel != OFX_ROBUST_NONE ? rs.scale : 1.0;
+    rb.c2 = rb.c * rb.c;
+    hipLaunchKernelGGL((k_terms<true, RobustArg>), dim3(g->nwg_terms), dim3(kBlk), 0, hs, *g, dc, m0, m1, add_reg, rb);
+  } else {
+    hipLaunchKernelGGL((k_terms<false>), dim3(g->nwg_terms), dim3(kBlk), 0, hs, *g, dc, m0, m1, add_reg);
+  }
 #ifdef OFX_STAMPS
   if (gn_iter > 0 && g->t_seen.time_since_epoch().count()) {
     g->react_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - g->t_seen).count();

@@ -663,6 +663,22 @@ def _(state, handle, n_nodes, num_iter):
             state.new_empty((5,), dtype=torch.int32), state.new_empty((num_iter, 4), dtype=torch.float64))
 
 
+@_op("gn_set_robust", mutates_args=("state",))
+def gn_set_robust(state: Tensor, handle: int, match_weights: Optional[Tensor], kernel: int, scale: float) -> None:
+    """ofx_gn_set_robust: per-match weights (f32 (M), or None = all 1) and a robust kernel (0 none / 1 Huber / 2 Tukey,
+    scale in metres) on the data rows of the following solves on this handle, until replaced; no weights and kernel 0
+    switch it off. The next gn_solve / gn_setup / gn_prepare on the handle copies the weights in its stream order:
+    match_weights must stay alive and unchanged until that call has been enqueued. No device work here."""
+    rb = _lib.GnRobust()
+    rb.match_weights, rb.kernel, rb.scale = ptr(match_weights), int(kernel), float(scale)
+    call("ofx_gn_set_robust", _lib.c_void_p(handle), byref(rb))
+
+
+@gn_set_robust.register_fake
+def _(state, handle, match_weights, kernel, scale):
+    return None
+
+
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
-       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate")
+       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate", "gn_set_robust")

@@ -243,7 +243,7 @@ class FusionPipeline:
         return tpos, conf
 
     def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
-                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None, photo=None):
+                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None, photo=None, robust=None):
         from .association import ProjectiveAssociator, icp_track, photo_params
         M = int(max_model_points)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
@@ -269,7 +269,8 @@ class FusionPipeline:
                                 self.prev_rot, self.prev_trans,
                                 self._motion(fi) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, M),
-                                depth_filter=depth_filter, **pho, **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
+                                depth_filter=depth_filter, robust=robust, **pho,
+                                **self._occlusion(*occ, M, fi.im[-1], True), **assoc)
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out
@@ -293,7 +294,7 @@ class FusionPipeline:
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
                    max_model_points=65536, w_min=1.0, rigid_iters=0, occlusion=False, splat_radius=None,
-                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, **assoc):
+                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, robust=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -337,15 +338,20 @@ class FusionPipeline:
         followed. The frame's colour image is fi.im[:3] (rgb in [0,1]). The volume model's colours are the fused ones
         (TSDFVolume.voxel_rgb of the sampled voxels); the canonical points take the source frame's rgb at their own
         pixels (set_source_colors(im), called by integrate_source; a ValueError without it, before any device work).
-        `mode` is ignored then: the target is always the vertex. None leaves the loop as it is."""
+        `mode` is ignored then: the target is always the vertex. None leaves the loop as it is.
+
+        robust (both models; None / "huber" / "tukey" / {"kernel", "scale"}): every solve of the tracking loop runs with
+        that robust kernel on its data rows (GaussNewtonSolver.optimize's robust=). None leaves the loop as it is."""
         from .association import photo_params
+        from .registration import robust_params
         photo_params(photo)   # (an unknown key is a TypeError before anything is touched)
+        robust_params(robust)
         if grow_every and model != "volume":
             raise ValueError("grow_every needs model='volume': the graph grows from the fused volume")
         if model == "volume":
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
                                       assoc, (occlusion, splat_radius, occl_margin), depth_filter, grow_every, grow,
-                                      photo)
+                                      photo, robust)
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
@@ -366,7 +372,7 @@ class FusionPipeline:
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
                                 self._motion(fi) if motion else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
-                                depth_filter=depth_filter, **pho,
+                                depth_filter=depth_filter, robust=robust, **pho,
                                 **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),
                                 **assoc)
         out["assoc"] = log

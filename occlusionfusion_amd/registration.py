@@ -33,6 +33,8 @@ GN_DEFAULTS = dict(num_iter=10, lambda_flow=0.0, lambda_depth=1.0, lambda_arap=0
 # reference's own LU, no PCG and no stop rule (pcg_* / precond_* ignored, pcg_iterations = 0); a larger graph raises
 # OfxError. "auto" never picks it.
 _PRECOND = {"cluster": 0, "schwarz": 1, "auto": 2, "direct": 3}
+# Robust kernels of the data rows (ofx_gn_set_robust) and their default scales in metres: the Huber delta and the Tukey c
+ROBUST_DEFAULTS = {"huber": 0.005, "tukey": 0.03}
 MAX_MATCHES_EVAL = 10000   # settings/custom_settings.py:36
 
 
@@ -44,6 +46,32 @@ def _t(x, device, dtype):
             return x   # per-frame fast path (host time: no .to / .contiguous dispatch)
         return x.to(device=device, dtype=dtype).contiguous()
     return torch.as_tensor(np.ascontiguousarray(x), device=device).to(dtype).contiguous()
+
+
+def robust_params(robust):
+    """The robust= keyword of optimize and of the tracking layers -> (OFX_ROBUST_* code, scale in metres), or None for
+    off (None / False / kernel "none"). "huber" / "tukey" take ROBUST_DEFAULTS' scale; a dict gives {"kernel": ...,
+    "scale": ...} (scale optional). Another key is a TypeError; an unknown kernel, or a scale that is not finite and
+    > 0, a ValueError."""
+    if robust is None or robust is False:
+        return None
+    if isinstance(robust, str):
+        kernel, scale = robust, None
+    else:
+        unknown = set(robust) - {"kernel", "scale"}
+        if unknown:
+            raise TypeError(f"unknown robust parameters {sorted(unknown)}")
+        if "kernel" not in robust:
+            raise ValueError("robust needs a kernel: 'huber' or 'tukey'")
+        kernel, scale = robust["kernel"], robust.get("scale")
+    if kernel is None or kernel == "none":
+        return None
+    if kernel not in ROBUST_DEFAULTS:
+        raise ValueError(f"unknown robust kernel {kernel!r}: one of {sorted(ROBUST_DEFAULTS)}")
+    scale = float(ROBUST_DEFAULTS[kernel] if scale is None else scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"robust scale must be finite and > 0 metres, got {scale}")
+    return _lib.ROBUST_KERNELS[kernel], scale
 
 
 def _prefetch_lead(num_iter):
@@ -68,6 +96,8 @@ class GaussNewtonSolver:
         # solver slots (handle, ordering token): a second one is made by the first prefetch (optimize(prefetch=)),
         # which sets up the next problem on the slot the current solve does not use
         self._slots = [self._new_slot()]
+        self._rob = [False]             # per slot: its handle holds match weights or a robust kernel (_set_robust)
+        self._last = 0                  # index of the last solve's slot
         self._cur = 0                   # slot of the next optimize()
         self._pending = [None, None]    # a prefetched problem's tensors, alive until its solve
         self._deferred = None           # defer_to_next_solve: (fn, handle) pending
@@ -219,6 +249,26 @@ class GaussNewtonSolver:
               int(mode), int(q.get("precond_every", 1)), _PRECOND[q.get("precond", "cluster")]]
         return fp, ip
 
+    def _match_weights(self, match_weights, M):
+        if match_weights is None:
+            return None
+        mw = _t(match_weights, self.device, torch.float32).reshape(-1)
+        if mw.shape[0] != M:
+            raise ValueError(f"match_weights has {mw.shape[0]} entries for {M} matches")
+        return mw
+
+    def _set_robust(self, slot, mw, rp):
+        """The slot's handle takes exactly this setting (torch.ops.ofx.gn_set_robust: mw a device f32 (M) tensor or None,
+        rp robust_params' pair or None); off on a handle that is off already is no call at all, so a solver that never
+        uses the feature issues what it always did."""
+        on = mw is not None or rp is not None
+        if not on and not self._rob[slot]:
+            return
+        h, st = self._slots[slot]
+        kernel, scale = rp if rp is not None else (0, 0.0)
+        torch.ops.ofx.gn_set_robust(st, h.value, mw, kernel, scale)
+        self._rob[slot] = on
+
     def _problem(self, graph_nodes, graph_edges, graph_edges_weights, target_node_position, node_confidence,
                  source_points, anchors, weights, target_points, intrinsics, target_px, target_py, prev_rot,
                  prev_trans, keep=True):
@@ -261,9 +311,16 @@ class GaussNewtonSolver:
 
     def optimize(self, graph_nodes, graph_edges, graph_edges_weights, target_node_position, node_confidence,
                  source_points, anchors, weights, target_points, intrinsics, target_px=None, target_py=None,
-                 prev_rot=None, prev_trans=None, sync=True, prefetch=None):
+                 prev_rot=None, prev_trans=None, sync=True, prefetch=None, match_weights=None, robust=None):
         """model.py:222-859 (batch item) through torch.ops.ofx.gn_solve. Returns torch device tensors (+ host
         convergence info if sync).
+
+        match_weights: (M) per-match weights, or None = all 1: match m's residual and Jacobian rows are multiplied by
+        it, as correspondence_weights does in DeformNet.forward (model.py:1338,1374-1378; its weight in the objective
+        is the square). robust: None, "huber", "tukey" or {"kernel": ..., "scale": metres} (ROBUST_DEFAULTS: Huber
+        0.005, Tukey 0.03) — an M-estimator on the data rows, reweighted at every GN step from the match's geometric
+        distance |p - tgt| (ofx_gn_set_robust). Every call sets the solving slot to what it asks, so neither carries over
+        to a later call; both None is the solve as it was.
 
         prefetch: the NEXT frame's problem as a dict of this method's argument names (graph_nodes ...
         target_points, optional target_px / target_py; intrinsics default to this call's; no pose). Its setup
@@ -271,10 +328,13 @@ class GaussNewtonSolver:
         host loop returns, ordered before this solve, and runs concurrently with this frame's tail
         (torch.ops.ofx.gn_prepare); the next optimize() with that problem (the same device tensors) then skips
         its setup. The prefetched tensors must not change until
-        that call."""
+        that call. The dict may carry match_weights / robust too: the next optimize() must then be given the same
+        weight tensor (device f32) and the same robust setting, or the prefetched setup is discarded."""
+        rp = robust_params(robust)
         args, N, M = self._problem(graph_nodes, graph_edges, graph_edges_weights, target_node_position,
                                    node_confidence, source_points, anchors, weights, target_points, intrinsics,
                                    target_px, target_py, prev_rot, prev_trans)
+        mw = self._match_weights(match_weights, M)
         fp, ip = self._plist()
         cur = self._cur
         h, st = self._slots[cur]
@@ -290,37 +350,42 @@ class GaussNewtonSolver:
                                      q["target_node_position"], q["node_confidence"], q["source_points"],
                                      q["anchors"], q["weights"], q["target_points"], q.get("intrinsics", intrinsics),
                                      q.get("target_px"), q.get("target_py"), None, None, keep=False)
+            pr = (self._match_weights(q.get("match_weights"), pa[5].shape[0]), robust_params(q.get("robust")))
             before = torch.cuda.Event()
             before.record()
             lead = int(self.prefetch_lead)
             if lead > 0:   # queued now, started by this solve at GN step num_iter - lead (or when it returns)
-                self._prefetch(pa, before, h, int(self.params["num_iter"]) - lead, fp, ip)
+                self._prefetch(pa, before, h, int(self.params["num_iter"]) - lead, fp, ip, pr)
+        self._set_robust(cur, mw, rp)
         if self._deferred is not None and self._deferred[1].value != h.value:   # (hooked on another slot)
             self.flush_deferred()
         out = torch.ops.ofx.gn_solve(st, h.value, *args, fp, ip)
         self.flush_deferred()   # (a deferred fn the solve never reached — no PCG wait — runs now; its exception too)
         self._pending[cur] = None
-        self._h, self._state = h, st
+        self._h, self._state, self._last = h, st, cur
         if prefetch is not None:
             if lead <= 0:
-                self._prefetch(pa, before, None, 0, fp, ip)
+                self._prefetch(pa, before, None, 0, fp, ip, pr)
             self._cur = 1 - cur
         return self._pack(out, sync)
 
-    def _prefetch(self, pa, before, trigger, step, fp, ip):
-        """Queue the next problem's setup on the other slot, ordered after `before` (torch.ops.ofx.gn_prepare)."""
+    def _prefetch(self, pa, before, trigger, step, fp, ip, pr=(None, None)):
+        """Queue the next problem's setup on the other slot, ordered after `before` (torch.ops.ofx.gn_prepare), under
+        the match weights / robust setting pr that the problem comes with."""
         nxt = 1 - self._cur
         if len(self._slots) < 2:
             self._slots.append(self._new_slot())
+            self._rob.append(False)
             call("ofx_gn_share_history", self._slots[1][0], self._slots[0][0])
         if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         h1, st1 = self._slots[nxt]
         with torch.cuda.stream(self._side):
             self._side.wait_event(before)
+            self._set_robust(nxt, *pr)
             torch.ops.ofx.gn_prepare(st1, h1.value, *pa[:11], pa[13], fp, ip, trigger.value if trigger else 0,
                                      max(step, 0))
-        self._pending[nxt] = pa
+        self._pending[nxt] = (pa, pr[0])
 
     def arap(self, graph_nodes, source_node_position, target_node_position, valid_nodes_mask, original_graph_nodes,
              graph_edges, graph_edges_weights, graph_clusters, R_current, t_current, sync=True, pcg_tol=1e-10):
@@ -351,6 +416,7 @@ class GaussNewtonSolver:
                                    np.zeros((0, 4), np.int32), np.zeros((0, 4), np.float32), z3, (1.0, 1.0, 0.0, 0.0),
                                    None, None, R_current, t_current)
         fp, ip = self._plist(mode=1, pcg_tol=pcg_tol)
+        self._set_robust(self._last, None, None)   # (no data rows to weigh)
         out = torch.ops.ofx.gn_solve(self._state, self._h.value, *args, fp, ip)
         res = self._pack(out, sync)
         t_init = self._keep[12]                              # prev_trans as uploaded
@@ -377,6 +443,7 @@ class GaussNewtonSolver:
                                    target_px, target_py, prev_rot, prev_trans)
         fp, ip = self._plist()
         h = self._h.value
+        self._set_robust(self._last, None, None)   # (the sharded solve takes no match weights)
         nnz, rows = (int(v) for v in torch.ops.ofx.gn_setup(self._state, h, *args, fp, ip))
         world = dist.get_world_size(group)
         rank = dist.get_rank(group)
@@ -510,9 +577,15 @@ class Registration:
             sel = np.sort(self.rng.choice(sel, self.max_matches, replace=False))
         idx = torch.as_tensor(sel, device=self.device, dtype=torch.int64)
         tloc, tconf = complete_node_motion_data if complete_node_motion_data is not None else (None, None)
+        # per-vertex correspondence weights of the target frame, if it brings any (DeformNet.forward's
+        # correspondence_weights, model.py:1338,1374-1378): the selected matches' go to the solve as match_weights
+        cw = target_frame_data.get("correspondence_weights") if isinstance(target_frame_data, dict) else None
+        if cw is not None:
+            cw = np.asarray(cw, np.float32).reshape(-1)[self.valid_source_verts][sel]
         out = self.solver.optimize(self.graph.nodes, self.graph.edges, self.graph.edges_weights, tloc, tconf,
                                    self.source_pcd[idx], self.point_anchors[idx], self.anchor_weight[idx],
-                                   tm[sel], self._intr4(), prev_rot=self.prev_rot, prev_trans=self.prev_trans)
+                                   tm[sel], self._intr4(), prev_rot=self.prev_rot, prev_trans=self.prev_trans,
+                                   match_weights=cw)
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)
@@ -528,7 +601,7 @@ class Registration:
 
     def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
               rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, depth_filter=None, photo=None,
-              **assoc):
+              robust=None, **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -558,7 +631,10 @@ class Registration:
         motion along the surface that depth alone cannot see. The frame's colour image is im[:3] (rgb in [0,1]); the
         model's colours are source_colors (update(colors=...), or update_from_volume() of a volume that fuses colour):
         without them a ValueError, before any device work. `mode` is ignored then: the target is always the vertex.
-        None is the loop as it was."""
+        None is the loop as it was.
+        robust (None / "huber" / "tukey" / {"kernel", "scale"}): every solve of the loop runs with that robust kernel on
+        its data rows (GaussNewtonSolver.optimize's robust=); None is the loop as it was."""
+        robust_params(robust)   # (refused before anything is touched)
         from .association import (ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track,
                                   photo_params)
         pho = {}
@@ -596,7 +672,7 @@ class Registration:
                                 self.source_pcd, nrm, self.point_anchors, self.anchor_weight, None, depth,
                                 self._intr4(), self.prev_rot, self.prev_trans, complete_node_motion_data, icp_iters,
                                 rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None),
-                                depth_filter=depth_filter, **pho, **occ, **assoc)
+                                depth_filter=depth_filter, robust=robust, **pho, **occ, **assoc)
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)

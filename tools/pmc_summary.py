@@ -22,7 +22,7 @@ KERNELS = {"k_pcg_iter": ("ofx::k_pcg_iter<true, false",), "k_as_apply": ("ofx::
            "k_as_proj2": ("ofx::k_as_proj2<",), "k_pcg_proj": ("ofx::k_pcg_proj<",),
            "k_as_invert": ("ofx::k_as_invert(",),
            "k_integrate_warp": ("ofx::k_integrate_pal4<true>", "ofx::k_integrate<true, true"),
-           "k_assemble": ("ofx::k_assemble(",), "k_terms": ("ofx::k_terms(",),
+           "k_assemble": ("ofx::k_assemble(",), "k_terms": ("ofx::k_terms(", "ofx::k_terms<false>"),
            "k_brick_cull": ("ofx::k_brick_cull(ofx::BrickGeom, ofx::BrickDiv",), "k_tile_max": ("ofx::k_tile_max(",)}
 
 
