@@ -24,6 +24,10 @@
  *   ofx_integrate_palette   same, node records staged per brick in LDS      warpfield.py:369-380, tsdf.py:442-494
  *   ofx_integrate_palette_cull  same, bricks that provably update nothing skipped (per-frame cull)
  *   ofx_integrate_points    TSDFVolume.integrate of given (deformed) points  tsdf.py:442-494
+ *   ofx_integrate*_w        (new) the four integrate entry points with a per-pixel observation-weight image and a cap on the
+ *                           accumulated weight; ofx_observation_weights makes the image — (no reference twin: the
+ *                           reference's fusion is the plain running average, tsdf.py:366-376, which stays the default.
+ *                           Restated op for op by tests/weighted_ref.py)
  *   ofx_raycast             (new) depth / normal / colour images of the TSDF  — (no reference twin)
  *   ofx_deform_points       ED_warp / deform_ED / deform_mesh / normals     NonRigidICP/model/geometry.py:9-25,
  *                                                                          registration_fusion.py:157-184, warpfield.py:312-367
@@ -246,6 +250,46 @@ int ofx_integrate_points(const ofx_volume_desc* desc, const ofx_camera* cam, con
                          const float* points, const int64_t* voxel_ids, const uint8_t* valid, int64_t n_points,
                          double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                          ofx_stream_t s);
+
+/* ---------------- Weighted integrate (new capability; the reference's is the plain running average, tsdf.py:366-376) ----
+ * The _w twins of the four integrate entry points: the same arguments plus an ofx_obs_weights, the same kernels
+ * instantiated with the weighted update, CPU semantics only. Restated op for op by tests/weighted_ref.py. Per voxel, at
+ * the pixel pix it already projects to and with every existing update condition unchanged:
+ *   o      = obs_im[pix]; !(o > 0 && o < +inf) (zero, negative, NaN, +inf): the voxel is not updated and not counted
+ *   obs    = f64(o) * obs_weight
+ *   w_sum  = f32(f64(w_old) + obs)
+ *   tsdf'  = f32((f64(f32(w_old * tsdf)) + obs * dist) / f64(w_sum))          (the unweighted flow with obs per voxel)
+ *   colour = as unweighted, with ow = f32(obs) and the divisor w_sum
+ *   weight' = fminf(w_sum, w_max)                                             (w_max = +inf: no cap)
+ * With obs_im == 1 everywhere and w_max = +inf the result equals the unweighted entry point's bit for bit. The brick
+ * cull is unchanged (it proves "no voxel updates" from the depth alone; a weight only removes updates).
+ * OFX_ERR_ARG: ow or obs_im NULL, obs_im not 4-byte aligned, !(w_max > 0) (a NaN included), OFX_SEM_PYCUDA. */
+typedef struct ofx_obs_weights {
+  const float* obs_im;  /* device f32[H*W], the depth image's size (e.g. ofx_observation_weights') */
+  float w_max;          /* cap on the stored weight, > 0; +inf = off */
+  float _pad;
+} ofx_obs_weights;
+int ofx_integrate_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                    int32_t warp, const float* packed_nodes, int32_t n_nodes, int32_t k,
+                    const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
+                    double obs_weight, float* tsdf, float* weight, float* color,
+                    uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s);
+int ofx_integrate_palette_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+                            const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
+                            const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
+                            const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
+                            double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                            const ofx_obs_weights* ow, ofx_stream_t s);
+int ofx_integrate_palette_cull_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+                                 const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
+                                 const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
+                                 const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
+                                 double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                                 float* tile_scratch, uint8_t* active, const ofx_obs_weights* ow, ofx_stream_t s);
+int ofx_integrate_points_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                           const float* points, const int64_t* voxel_ids, const uint8_t* valid, int64_t n_points,
+                           double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                           const ofx_obs_weights* ow, ofx_stream_t s);
 
 /* TSDF raycast (new capability; the reference has none — parity unpinned, restated by the oracle): per pixel
  * of `cam` (identity pose), march the ray from max(z_near, volume entry) to min(z_far, volume exit) through the
@@ -502,6 +546,28 @@ typedef struct ofx_prepare_params {
 int ofx_prepare_depth(const void* depth, int32_t is_u16, int32_t height, int32_t width, const ofx_camera* cam,
                       const ofx_prepare_params* prm, float* depth_out, float* point_image, float* normal_image,
                       ofx_stream_t s);
+
+/* Observation-weight map of a frame for the weighted integrate (ofx_integrate*_w), from ofx_prepare_depth's vertex map p
+ * and normal map n (planar f32[3*H*W] each). Restated op for op by tests/weighted_ref.py. Per pixel (f32, no contraction,
+ * the summation order as written, sqrt and divisions correctly rounded):
+ *   hole (!(p_z > 0), a NaN included)                 : 0
+ *   no normal (n all zero: the gate's codes 3 / 4 — border, a neighbour hole, a depth edge beyond edge_max)
+ *                                                     : edge_weight
+ *   else c = -((n_x*p_x + n_y*p_y) + n_z*p_z) / sqrt((p_x*p_x + p_y*p_y) + p_z*p_z), clamped to [0, 1], a NaN -> 0
+ *        a = 1, c or c*c for cos_power 0 / 1 / 2
+ *        s = 1 if z_ref == 0, else min(1, r*r) with r = z_ref / p_z
+ *        w = max(w_floor, a*s)
+ * obs_im f32[H*W]: every element is written on every call. Stream-ordered: no handle, no allocation, no host sync (one
+ * launch). OFX_ERR_ARG: cos_power outside {0, 1, 2}; a negative or non-finite z_ref, w_floor or edge_weight; a NULL or
+ * not 4-byte aligned buffer; height or width < 1 or height * width >= 2^31. */
+typedef struct ofx_obs_params {
+  int32_t cos_power;   /* 0, 1 or 2 */
+  float z_ref;         /* metres; 0 = no range term */
+  float w_floor;       /* the least weight of a pixel that has a normal */
+  float edge_weight;   /* the weight of a pixel with depth but no normal (0: flying pixels are not fused) */
+} ofx_obs_params;
+int ofx_observation_weights(const float* point_image, const float* normal_image, int32_t height, int32_t width,
+                            const ofx_obs_params* prm, float* obs_im, ofx_stream_t s);
 
 /* ---------------- Photometric correspondence search (new capability; the reference has none — parity unpinned) ----------------
  * The stand-in for the reference's flow network, as ofx_associate is for its landmark matcher: each warped model point looks in

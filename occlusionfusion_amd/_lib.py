@@ -59,6 +59,14 @@ class PrepareParams(ctypes.Structure):
 PREPARE_RMAX = 4   # OFX_PREPARE_RMAX (include/ofx.h)
 
 
+class ObsWeights(ctypes.Structure):
+    _fields_ = [("obs_im", P), ("w_max", c_float), ("_pad", c_float)]
+
+
+class ObsParams(ctypes.Structure):
+    _fields_ = [("cos_power", c_int32), ("z_ref", c_float), ("w_floor", c_float), ("edge_weight", c_float)]
+
+
 class GnParams(ctypes.Structure):
     _fields_ = [("num_iter", c_int32), ("use_edge_weighting", c_int32), ("pcg_max_iter", c_int32), ("pcg_warm", c_int32),
                 ("lambda_flow", c_double), ("lambda_depth", c_double), ("lambda_arap", c_double),
@@ -108,6 +116,12 @@ _SIGS = {
     "ofx_integrate_palette": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P],
     "ofx_integrate_palette_cull": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P,
                                    P, P],
+    "ofx_integrate_w": [P, P, P, P, c_int32, P, c_int32, c_int32, P, c_int32, P, P, c_double, P, P, P, P, P, P],
+    "ofx_integrate_points_w": [P, P, P, P, P, P, P, c_int64, c_double, P, P, P, P, P, P],
+    "ofx_integrate_palette_w": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P, P],
+    "ofx_integrate_palette_cull_w": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P,
+                                     P, P, P],
+    "ofx_observation_weights": [P, P, c_int32, c_int32, P, P, P],
     "ofx_deform_points": [P, c_int64, P, P, P, c_int32, P, c_int32, c_int32, P, P],
     "ofx_deform_points_lbs": [P, c_int64, P, P, P, c_int32, P, P, c_int32, P, P],
     "ofx_visibility": [P, c_int64, P, P, c_double, P, P, P],

@@ -57,17 +57,35 @@ __device__ __forceinline__ bool f32_round_safe(double t, double err, float& out)
   return t - err > lo && t + err < hi;
 }
 
+// Weighted integrate (ofx_integrate*_w): the per-pixel observation weights, read at the pixel the voxel projects to, and
+// the cap on the stored weight (+inf: none). Kernels and device functions take it behind a template flag WT; with WT
+// false the argument is dead and the code is the unweighted kernel's.
+struct ObsW {
+  const float* __restrict__ im;   // f32[H*W]
+  float w_max;
+};
+// the kernels' last parameter: ObsW for WT, an empty struct otherwise
+struct NoObs {};
+template <bool WT> struct ObsArg { using type = NoObs; };
+template <> struct ObsArg<true> { using type = ObsW; };
+template <bool WT> using obs_arg_t = typename ObsArg<WT>::type;
+// a usable observation weight: finite and > 0 (zero, negative, NaN and +inf all leave the voxel alone)
+__device__ __forceinline__ bool obs_ok(float o) { return o > 0.f && o < __builtin_inff(); }
+
 // One voxel update; returns 1 if the voxel was integrated. Reference semantics (tsdf.py:351-376,
 // 479-494; numba f64 promotion), with three of the seven f64 divisions replaced by products with a
 // reciprocal: (X·fx)/Z and (Y·fy)/Z use 1/Z, dd/trunc uses 1/trunc, the SDF quotient uses 1/w_new.
 // Each replacement perturbs the f64 value by a few ulp at most; the result is used only where that
 // cannot change a rounding (pixel: not within 1e-9 of a half-integer; SDF: its f32 rounding interval
 // contains the whole error bound) — otherwise the exact division path runs. Bit-identical results.
+// WT: obs is scaled by the pixel's observation weight (the product in f64) and the stored weight is capped; the
+// certificates hold for any f64 obs > 0 and f32 w_old (DESIGN §6 "Weighted integrate").
+template <bool WT>
 __device__ __forceinline__ int update_voxel(const CamD& c, const float* __restrict__ depth,
                                             const float* __restrict__ color_im, double trunc, double itrunc,
                                             double obs, float x, float y, float z, int64_t vi,
                                             float* __restrict__ tsdf, float* __restrict__ weight,
-                                            float* __restrict__ color) {
+                                            float* __restrict__ color, const obs_arg_t<WT>& ow) {
   const double X = x, Y = y, Z = z;
   if (!(Z > 0.0)) return 0;
   const double nx = X * c.fx, ny = Y * c.fy;
@@ -85,6 +103,11 @@ __device__ __forceinline__ int update_voxel(const CamD& c, const float* __restri
   float d = depth[pix];
   double dd = (double)d - Z;
   if (!(d > 0.f && dd >= -trunc)) return 0;
+  if constexpr (WT) {
+    const float o = ow.im[pix];
+    if (!obs_ok(o)) return 0;
+    obs = (double)o * obs;
+  }
   const float w_old = weight[vi];
   const float t_old = tsdf[vi];
   float w_new = (float)((double)w_old + obs);
@@ -100,7 +123,8 @@ __device__ __forceinline__ int update_voxel(const CamD& c, const float* __restri
     const double dist = fmin(1.0, dd / trunc);
     t_new = (float)(((double)prod + obs * dist) / wn);
   }
-  weight[vi] = w_new;
+  if constexpr (WT) weight[vi] = fminf(w_new, ow.w_max);
+  else weight[vi] = w_new;
   tsdf[vi] = t_new;
   if (color) {
     const float C = 65536.0f;
@@ -295,7 +319,8 @@ __device__ __forceinline__ void count_updates(int n, uint32_t* counts) {
 // register budget is capped at 64 VGPRs for full occupancy (87 -> 77 us at 512^3). Prefetching the
 // voxels' tsdf/weight/colour ahead of the palette barrier is slower: vmcnt retires in order, so the
 // barrier would wait on those HBM loads.
-template <bool WARP, bool PAL, bool PYC>
+// WT: the weighted form (observation-weight image + weight cap: update_voxel), CPU semantics only.
+template <bool WARP, bool PAL, bool PYC, bool WT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_integrate(BrickGeom g, CamD c, const float* __restrict__ depth,
                                                     const float* __restrict__ color_im,
                                                     const float4* __restrict__ nodes, int K,
@@ -306,7 +331,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
                                                     const int32_t* __restrict__ pal_n,
                                                     const uchar4* __restrict__ local, double trunc, double obs,
                                                     float* __restrict__ tsdf, float* __restrict__ weight,
-                                                    float* __restrict__ color, uint32_t* counter) {
+                                                    float* __restrict__ color, uint32_t* counter, obs_arg_t<WT> ow) {
+  static_assert(!(PYC && WT), "the weighted integrate has CPU semantics only");
   __shared__ float4 s_node[PAL ? 4 * kPal : 1];
   const int64_t slot = blockIdx.x;
   const int64_t b = (WARP || list) ? (int64_t)list[slot] : slot;   // source frame: optional brick list (hash shard)
@@ -355,7 +381,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     }
     if (PYC) n_upd += update_voxel_pycuda(c, depth, color_im, (float)trunc, (float)obs, x, y, z, b * kBrickVox + l, tsdf,
                                           weight, color);
-    else n_upd += update_voxel(c, depth, color_im, trunc, 1.0 / trunc, obs, x, y, z, b * kBrickVox + l, tsdf, weight, color);
+    else n_upd += update_voxel<WT>(c, depth, color_im, trunc, 1.0 / trunc, obs, x, y, z, b * kBrickVox + l, tsdf, weight,
+                                   color, ow);
   }
   count_updates(n_upd, counter);
 }
@@ -375,14 +402,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 #define OFX_INT_WPE 7   // (tuning builds: -DOFX_INT_WPE=n; 7: 72 VGPRs, 12 B of scratch, 90.0 -> 84.9 us against 6;
                         // 8: 64 VGPRs, 56 B of scratch, 146 us: profiles/r05_ab.json)
 #endif
-template <bool COLOR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_INT_WPE))) void k_integrate_pal4(
+#ifndef OFX_INT_WPE_W
+#define OFX_INT_WPE_W 7   // the weighted form's own budget (one more live value through trip 3): DESIGN §6
+#endif
+// WT: the pixel's observation weight is one more load of trip 3, beside depth[pc] at the same pixel
+template <bool COLOR, bool WT = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WT ? OFX_INT_WPE_W : OFX_INT_WPE))) void k_integrate_pal4(
     BrickGeom g, BrickDiv bd, CamD c, const float* __restrict__ depth, const float* __restrict__ color_im,
     const float4* __restrict__ nodes, int n_nodes, const int32_t* __restrict__ list,
     const ushort4* __restrict__ anchors, const float4* __restrict__ weights, const uint16_t* __restrict__ pal_ids,
     const int32_t* __restrict__ pal_n, const uchar4* __restrict__ local, double trunc, double itrunc, double obs,
     float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ color, uint32_t* counter,
-    const uint8_t* __restrict__ active) {
+    const uint8_t* __restrict__ active, obs_arg_t<WT> ow) {
   __shared__ float4 s_node[4 * kPal];
   __shared__ float s_xyz[3 * kBrick];   // vox2world of the brick's 8 x, y and z coordinates
   __shared__ uint32_t s_cnt[4];
@@ -462,11 +493,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_INT_WPE
     if (pz > 0.f) pix[h] = pixel_of(c, px, py, pz);
   }
   // ---- trip 3 (skin-valid voxels; pixel 0 stands in for the unprojected ones)
-  float d[2], nc[2], oc[2];
+  float d[2], nc[2], oc[2], ob[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int pc = pix[h] >= 0 ? pix[h] : 0;
     d[h] = depth[pc];
+    if constexpr (WT) ob[h] = ow.im[pc];
     if (COLOR) { nc[h] = color_im[pc]; oc[h] = color[b * (uint32_t)kBrickVox + (act[h] ? (uint32_t)(tid + 256 * h) : 0u)]; }
   }
   // the loaded values pass through an empty asm: both halves' loads are issued before the first use (else the second
@@ -475,6 +507,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_INT_WPE
   for (int h = 0; h < 2; ++h) {
     if (COLOR) asm volatile("" : "+v"(d[h]), "+v"(nc[h]), "+v"(oc[h]));
     else asm volatile("" : "+v"(d[h]));
+    if constexpr (WT) asm volatile("" : "+v"(ob[h]));
   }
   asm volatile("" ::: "memory");
   uint32_t n_upd = 0;
@@ -483,10 +516,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFX_INT_WPE
     bool upd = false;
     if (pix[h] >= 0) {
       const double dd = (double)d[h] - (double)zw[h];
-      if (d[h] > 0.f && dd >= -trunc) {
+      bool take = d[h] > 0.f && dd >= -trunc;
+      if constexpr (WT) take = take && obs_ok(ob[h]);
+      if (take) {
         float wn, tn, cn;
-        sdf_color_update(dd, trunc, itrunc, obs, w_old[h], t_old[h], COLOR ? nc[h] : 0.f, COLOR ? oc[h] : 0.f,
-                         COLOR, wn, tn, cn);
+        sdf_color_update(dd, trunc, itrunc, WT ? (double)ob[h] * obs : obs, w_old[h], t_old[h], COLOR ? nc[h] : 0.f,
+                         COLOR ? oc[h] : 0.f, COLOR, wn, tn, cn);
+        if constexpr (WT) wn = fminf(wn, ow.w_max);
         weight[vb + 256 * h] = wn;
         tsdf[vb + 256 * h] = tn;
         if (COLOR) color[vb + 256 * h] = cn;
@@ -649,11 +685,11 @@ __global__ __launch_bounds__(256) void k_brick_cull(BrickGeom g, BrickDiv bd, Ca
 // brick's 8x8 u-table and 8x8 v-table exactly in f64 (the reference expression, 128 lanes, one each) plus
 // the 24 world coordinates, and every voxel then looks its pixel up in LDS. brick_list (may be NULL: all
 // bricks of the shard) restricts the pass to the listed bricks (hash-bucket shards). 2 voxels per thread.
-template <bool COLOR>
+template <bool COLOR, bool WT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_integrate_src(
     BrickGeom g, BrickDiv bd, CamD c, const float* __restrict__ depth, const float* __restrict__ color_im,
     const int32_t* __restrict__ list, double trunc, double itrunc, double obs, float* __restrict__ tsdf,
-    float* __restrict__ weight, float* __restrict__ color, uint32_t* counter) {
+    float* __restrict__ weight, float* __restrict__ color, uint32_t* counter, obs_arg_t<WT> ow) {
   __shared__ int s_u[kBrick * kBrick], s_v[kBrick * kBrick];
   __shared__ float s_xyz[3 * kBrick];
   __shared__ uint32_t s_cnt[4];
@@ -699,11 +735,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     const int uu = s_u[((tid >> 6) + 4 * h) * kBrick + lz];
     pix[h] = (in[h] && uu >= 0 && vv >= 0) ? vv * c.W + uu : -1;
   }
-  float d[2], nc[2], oc[2];
+  float d[2], nc[2], oc[2], ob[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     if (pix[h] >= 0) {
       d[h] = depth[pix[h]];
+      if constexpr (WT) ob[h] = ow.im[pix[h]];
       if (COLOR) { nc[h] = color_im[pix[h]]; oc[h] = color[vb + 256 * h]; }
     }
   }
@@ -714,10 +751,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     bool upd = false;
     if (pix[h] >= 0) {
       const double dd = (double)d[h] - (double)z;
-      if (d[h] > 0.f && dd >= -trunc) {
+      bool take = d[h] > 0.f && dd >= -trunc;
+      if constexpr (WT) take = take && obs_ok(ob[h]);
+      if (take) {
         float wn, tn, cn;
-        sdf_color_update(dd, trunc, itrunc, obs, w_old[h], t_old[h], COLOR ? nc[h] : 0.f, COLOR ? oc[h] : 0.f,
-                         COLOR, wn, tn, cn);
+        sdf_color_update(dd, trunc, itrunc, WT ? (double)ob[h] * obs : obs, w_old[h], t_old[h], COLOR ? nc[h] : 0.f,
+                         COLOR ? oc[h] : 0.f, COLOR, wn, tn, cn);
+        if constexpr (WT) wn = fminf(wn, ow.w_max);
         weight[vb + 256 * h] = wn;
         tsdf[vb + 256 * h] = tn;
         if (COLOR) color[vb + 256 * h] = cn;
@@ -737,14 +777,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 // from WarpField.deform_tsdf, warpfield.py:369-380): point p updates voxel vox[p] (C-order id), with the
 // same arithmetic as the fused kernels (pixel_of / sdf_color_update, or the pycuda form). Points of voxels
 // outside this shard are ignored. Voxel ids must be distinct (one writer per voxel).
-template <bool PYC>
+template <bool PYC, bool WT = false>
 __global__ __launch_bounds__(256) void k_integrate_points(BrickGeom g, CamD c, const float* __restrict__ depth,
                                                           const float* __restrict__ color_im,
                                                           const float* __restrict__ pts, const int64_t* __restrict__ vox,
                                                           const uint8_t* __restrict__ valid, int64_t n, double trunc,
                                                           double itrunc, double obs, float* __restrict__ tsdf,
                                                           float* __restrict__ weight, float* __restrict__ color,
-                                                          uint32_t* n_updated) {
+                                                          uint32_t* n_updated, obs_arg_t<WT> ow) {
+  static_assert(!(PYC && WT), "the weighted integrate has CPU semantics only");
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int upd = 0;
   if (p < n && (!valid || valid[p])) {
@@ -762,10 +803,18 @@ __global__ __launch_bounds__(256) void k_integrate_points(BrickGeom g, CamD c, c
         if (pix >= 0) {
           const float d = depth[pix];
           const double dd = (double)d - (double)z;
-          if (d > 0.f && dd >= -trunc) {
+          bool take = d > 0.f && dd >= -trunc;
+          double ov = obs;
+          if constexpr (WT) {
+            const float o = ow.im[pix];
+            take = take && obs_ok(o);
+            ov = (double)o * obs;
+          }
+          if (take) {
             float wn, tn, cn;
-            sdf_color_update(dd, trunc, itrunc, obs, weight[vi], tsdf[vi], color ? color_im[pix] : 0.f,
+            sdf_color_update(dd, trunc, itrunc, ov, weight[vi], tsdf[vi], color ? color_im[pix] : 0.f,
                              color ? color[vi] : 0.f, color != nullptr, wn, tn, cn);
+            if constexpr (WT) wn = fminf(wn, ow.w_max);
             weight[vi] = wn;
             tsdf[vi] = tn;
             if (color) color[vi] = cn;
@@ -886,6 +935,163 @@ struct IntTimer {
     else                                                                                                  \
       hipLaunchKernelGGL(kernel, grid, block, shm, stream, __VA_ARGS__);                                  \
   } while (0)
+
+// the weighted entry points' extra argument: checked, then handed to the kernels as ObsW
+int check_obs(const ofx_volume_desc* desc, const ofx_obs_weights* ow) {
+  OFX_CHECK_ARG(ow && ow->obs_im, "null observation weights");
+  OFX_CHECK_ARG((reinterpret_cast<uintptr_t>(ow->obs_im) & 3) == 0, "obs_im must be 4-byte aligned");
+  OFX_CHECK_ARG(ow->w_max > 0.f, "w_max (%g) must be > 0 (+inf: no cap)", (double)ow->w_max);
+  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU, "the weighted integrate has CPU semantics only (semantics %d)",
+                desc->semantics);
+  return OFX_OK;
+}
+
+// The bodies of ofx_integrate* and their _w twins: ow == nullptr launches exactly what the unweighted entry points
+// always launched; with ow the WT instantiation of the same kernel runs.
+int integrate_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                   int32_t warp, const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
+                   int32_t n_list, const uint16_t* anchors, const float* weights, double obs_weight, float* tsdf,
+                   float* weight, float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
+  BrickGeom g;
+  int st = make_geom(desc, &g);
+  if (st) return st;
+  OFX_CHECK_ARG(cam && depth && tsdf && weight, "null buffer");
+  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
+  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
+  CamD c = make_cam(cam);
+  hipStream_t hs = as_stream(s);
+  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
+  const bool pyc = desc->semantics == OFX_SEM_PYCUDA;
+  ObsW w{};
+  if (ow) {
+    if ((st = check_obs(desc, ow))) return st;
+    w = ObsW{ow->obs_im, ow->w_max};
+  }
+  if (!warp && !pyc && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC")) {
+    const unsigned nb = brick_list ? (unsigned)n_list : (unsigned)g.n_bricks;
+    if (nb == 0) return OFX_OK;
+    if (ow) {
+      if (color)
+        hipLaunchKernelGGL((k_integrate_src<true, true>), dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
+                           brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
+                           n_updated, w);
+      else
+        hipLaunchKernelGGL((k_integrate_src<false, true>), dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
+                           brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
+                           n_updated, w);
+    } else if (color)
+      hipLaunchKernelGGL(k_integrate_src<true>, dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
+                         brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
+                         n_updated, NoObs{});
+    else
+      hipLaunchKernelGGL(k_integrate_src<false>, dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
+                         brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
+                         n_updated, NoObs{});
+  } else if (!warp) {
+    // generic source-frame form: pycuda semantics, shards of >= 2^31 voxels, or the OFX_INT_GENERIC A/B; a brick
+    // list (hash shard) is walked as in the warped form
+    OFX_CHECK_ARG(brick_list == nullptr || (n_list >= 0 && n_list <= g.n_bricks), "bad n_list");
+    const unsigned nb = brick_list ? (unsigned)n_list : (unsigned)g.n_bricks;
+    if (nb == 0) return OFX_OK;
+    if (ow)
+      hipLaunchKernelGGL((k_integrate<false, false, false, true>), dim3(nb), dim3(256), 0, hs, g, c, depth, color_im,
+                         (const float4*)nullptr, 1, brick_list, (const ushort4*)nullptr, (const float4*)nullptr,
+                         (const uint16_t*)nullptr, (const int32_t*)nullptr, (const uchar4*)nullptr, desc->trunc_margin,
+                         obs_weight, tsdf, weight, color, n_updated, w);
+    else
+      hipLaunchKernelGGL(pyc ? (k_integrate<false, false, true>) : (k_integrate<false, false, false>),
+                         dim3(nb), dim3(256), 0, hs, g, c, depth,
+                         color_im, (const float4*)nullptr, 1, brick_list, (const ushort4*)nullptr,
+                         (const float4*)nullptr, (const uint16_t*)nullptr, (const int32_t*)nullptr,
+                         (const uchar4*)nullptr, desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, NoObs{});
+  } else {
+    OFX_CHECK_ARG(k >= 1 && k <= 4 && n_nodes >= k, "bad k/n_nodes");
+    OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
+    if (n_list == 0) return OFX_OK;
+    OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights, "null warp buffer");
+    IntTimer timer;
+    if (ow)
+      OFX_TIMED_LAUNCH(timer, (k_integrate<true, false, false, true>), dim3((unsigned)n_list), dim3(256), 0, hs, g, c, depth,
+                       color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
+                       (const float4*)weights, (const uint16_t*)nullptr, (const int32_t*)nullptr,
+                       (const uchar4*)nullptr, desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, w);
+    else
+      OFX_TIMED_LAUNCH(timer, pyc ? (k_integrate<true, false, true>) : (k_integrate<true, false, false>), dim3((unsigned)n_list),
+                       dim3(256), 0, hs, g, c, depth, color_im,
+                       (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors, (const float4*)weights,
+                       (const uint16_t*)nullptr, (const int32_t*)nullptr, (const uchar4*)nullptr,
+                       desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, NoObs{});
+  }
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+int integrate_palette_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                           const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
+                           int32_t n_list, const uint16_t* anchors, const float* weights, const uint16_t* pal_ids,
+                           const int32_t* pal_n, const uint8_t* local_anchors, double obs_weight, float* tsdf,
+                           float* weight, float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
+  BrickGeom g;
+  int st = make_geom(desc, &g);
+  if (st) return st;
+  OFX_CHECK_ARG(cam && depth, "null camera/depth");
+  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
+  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
+  OFX_CHECK_ARG(k >= 1 && k <= 4 && n_nodes >= k, "bad k/n_nodes");
+  OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
+  ObsW w{};
+  if (ow) {
+    if ((st = check_obs(desc, ow))) return st;
+    w = ObsW{ow->obs_im, ow->w_max};
+  }
+  if (n_list == 0) return OFX_OK;
+  OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights && pal_ids && pal_n && local_anchors,
+                "null warp/palette buffer");
+  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
+  IntTimer timer;
+  if (desc->semantics == OFX_SEM_CPU && k == 4 && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC")) {
+    if (ow) {
+      if (color)
+        OFX_TIMED_LAUNCH(timer, (k_integrate_pal4<true, true>), dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g,
+                         make_div(g), make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
+                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
+                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
+                         (const uint8_t*)nullptr, w);
+      else
+        OFX_TIMED_LAUNCH(timer, (k_integrate_pal4<false, true>), dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g,
+                         make_div(g), make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
+                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
+                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
+                         (const uint8_t*)nullptr, w);
+    } else if (color)
+      OFX_TIMED_LAUNCH(timer, k_integrate_pal4<true>, dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_div(g),
+                         make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
+                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
+                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
+                         (const uint8_t*)nullptr, NoObs{});
+    else
+      OFX_TIMED_LAUNCH(timer, k_integrate_pal4<false>, dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_div(g),
+                         make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
+                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
+                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
+                         (const uint8_t*)nullptr, NoObs{});
+    OFX_LAUNCH_CHECK();
+    return OFX_OK;
+  }
+  if (ow)
+    OFX_TIMED_LAUNCH(timer, (k_integrate<true, true, false, true>), dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g,
+                     make_cam(cam), depth, color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
+                     (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin, obs_weight,
+                     tsdf, weight, color, n_updated, w);
+  else
+    OFX_TIMED_LAUNCH(timer, desc->semantics == OFX_SEM_PYCUDA ? (k_integrate<true, true, true>) : (k_integrate<true, true, false>),
+                     dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_cam(cam),
+                     depth, color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
+                     (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
+                     obs_weight, tsdf, weight, color, n_updated, NoObs{});
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -912,52 +1118,17 @@ int ofx_integrate(const ofx_volume_desc* desc, const ofx_camera* cam, const floa
                   int32_t warp, const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
                   int32_t n_list, const uint16_t* anchors, const float* weights, double obs_weight, float* tsdf,
                   float* weight, float* color, uint32_t* n_updated, ofx_stream_t s) {
-  BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  OFX_CHECK_ARG(cam && depth && tsdf && weight, "null buffer");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  CamD c = make_cam(cam);
-  hipStream_t hs = as_stream(s);
-  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
-  const bool pyc = desc->semantics == OFX_SEM_PYCUDA;
-  if (!warp && !pyc && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC")) {
-    const unsigned nb = brick_list ? (unsigned)n_list : (unsigned)g.n_bricks;
-    if (nb == 0) return OFX_OK;
-    if (color)
-      hipLaunchKernelGGL(k_integrate_src<true>, dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
-                         brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
-                         n_updated);
-    else
-      hipLaunchKernelGGL(k_integrate_src<false>, dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
-                         brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
-                         n_updated);
-  } else if (!warp) {
-    // generic source-frame form: pycuda semantics, shards of >= 2^31 voxels, or the OFX_INT_GENERIC A/B; a brick
-    // list (hash shard) is walked as in the warped form
-    OFX_CHECK_ARG(brick_list == nullptr || (n_list >= 0 && n_list <= g.n_bricks), "bad n_list");
-    const unsigned nb = brick_list ? (unsigned)n_list : (unsigned)g.n_bricks;
-    if (nb == 0) return OFX_OK;
-    hipLaunchKernelGGL(pyc ? (k_integrate<false, false, true>) : (k_integrate<false, false, false>),
-                       dim3(nb), dim3(256), 0, hs, g, c, depth,
-                       color_im, (const float4*)nullptr, 1, brick_list, (const ushort4*)nullptr,
-                       (const float4*)nullptr, (const uint16_t*)nullptr, (const int32_t*)nullptr,
-                       (const uchar4*)nullptr, desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated);
-  } else {
-    OFX_CHECK_ARG(k >= 1 && k <= 4 && n_nodes >= k, "bad k/n_nodes");
-    OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
-    if (n_list == 0) return OFX_OK;
-    OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights, "null warp buffer");
-    IntTimer timer;
-    OFX_TIMED_LAUNCH(timer, pyc ? (k_integrate<true, false, true>) : (k_integrate<true, false, false>), dim3((unsigned)n_list),
-                       dim3(256), 0, hs, g, c, depth, color_im,
-                       (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors, (const float4*)weights,
-                       (const uint16_t*)nullptr, (const int32_t*)nullptr, (const uchar4*)nullptr,
-                       desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated);
-  }
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  return integrate_impl(desc, cam, depth, color_im, warp, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                        obs_weight, tsdf, weight, color, n_updated, nullptr, s);
+}
+
+int ofx_integrate_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                    int32_t warp, const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
+                    int32_t n_list, const uint16_t* anchors, const float* weights, double obs_weight, float* tsdf,
+                    float* weight, float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
+  OFX_CHECK_ARG(ow, "null observation weights");
+  return integrate_impl(desc, cam, depth, color_im, warp, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                        obs_weight, tsdf, weight, color, n_updated, ow, s);
 }
 
 int ofx_integrate_palette(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
@@ -966,60 +1137,42 @@ int ofx_integrate_palette(const ofx_volume_desc* desc, const ofx_camera* cam, co
                           const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
                           double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                           ofx_stream_t s) {
-  BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  OFX_CHECK_ARG(cam && depth, "null camera/depth");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  OFX_CHECK_ARG(k >= 1 && k <= 4 && n_nodes >= k, "bad k/n_nodes");
-  OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
-  if (n_list == 0) return OFX_OK;
-  OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights && pal_ids && pal_n && local_anchors,
-                "null warp/palette buffer");
-  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
-  IntTimer timer;
-  if (desc->semantics == OFX_SEM_CPU && k == 4 && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC")) {
-    if (color)
-      OFX_TIMED_LAUNCH(timer, k_integrate_pal4<true>, dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_div(g),
-                         make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
-                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
-                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                         (const uint8_t*)nullptr);
-    else
-      OFX_TIMED_LAUNCH(timer, k_integrate_pal4<false>, dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_div(g),
-                         make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
-                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
-                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                         (const uint8_t*)nullptr);
-    OFX_LAUNCH_CHECK();
-    return OFX_OK;
-  }
-  OFX_TIMED_LAUNCH(timer, desc->semantics == OFX_SEM_PYCUDA ? (k_integrate<true, true, true>) : (k_integrate<true, true, false>),
-                     dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_cam(cam),
-                     depth, color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
-                     (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
-                     obs_weight, tsdf, weight, color, n_updated);
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  return integrate_palette_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                                pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, nullptr, s);
 }
 
-int ofx_integrate_palette_cull(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+int ofx_integrate_palette_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+                            const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
+                            const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
+                            const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
+                            double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                            const ofx_obs_weights* ow, ofx_stream_t s) {
+  OFX_CHECK_ARG(ow, "null observation weights");
+  return integrate_palette_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                                pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, ow, s);
+}
+
+static int integrate_cull_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
                                const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
                                const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
                                const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
                                double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
-                               float* tile_scratch, uint8_t* active, ofx_stream_t s) {
+                               float* tile_scratch, uint8_t* active, const ofx_obs_weights* ow, ofx_stream_t s) {
   BrickGeom g;
   int st = make_geom(desc, &g);
   if (st) return st;
   OFX_CHECK_ARG(cam && depth, "null camera/depth");
   OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
+  ObsW w{};
+  if (ow) {
+    if ((st = check_obs(desc, ow))) return st;
+    w = ObsW{ow->obs_im, ow->w_max};
+  }
   const bool fast = desc->semantics == OFX_SEM_CPU && k == 4 && g.n_bricks * kBrickVox < (1ll << 31) &&
                     !getenv("OFX_INT_GENERIC");
   if (!fast || !tile_scratch || !active)   // the cull serves the CPU-semantics K = 4 palette kernel only
-    return ofx_integrate_palette(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
-                                 weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, s);
+    return integrate_palette_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
+                                  weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, ow, s);
   OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
   OFX_CHECK_ARG(n_nodes >= k, "bad k/n_nodes");
   OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
@@ -1040,21 +1193,76 @@ int ofx_integrate_palette_cull(const ofx_volume_desc* desc, const ofx_camera* ca
   hipLaunchKernelGGL(k_brick_cull, dim3((unsigned)((n_list + 15) / 16)), dim3(256), 0, hs, g, bd, c,
                      (const float4*)packed_nodes, n_nodes, brick_list, pal_ids, pal_n, n_list,
                      (const float*)tile_scratch, TW, TH, desc->trunc_margin, active);
-  auto launch = [&](auto kern) {
+  // (extra: the kernel's last argument, NoObs or the weighted form's ObsW — the cull itself reads the depth alone: a weight only removes updates)
+  auto launch = [&](auto kern, auto... extra) {
     if (timer.e0)
       hipExtLaunchKernelGGL(kern, dim3((unsigned)n_list), dim3(256), 0, hs, nullptr, timer.e1, 0, g, bd, c, depth,
                             color_im, (const float4*)packed_nodes, n_nodes, brick_list, (const ushort4*)anchors,
                             (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
                             1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                            (const uint8_t*)active);
+                            (const uint8_t*)active, extra...);
     else
       hipLaunchKernelGGL(kern, dim3((unsigned)n_list), dim3(256), 0, hs, g, bd, c, depth, color_im,
                          (const float4*)packed_nodes, n_nodes, brick_list, (const ushort4*)anchors,
                          (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
-                         1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, (const uint8_t*)active);
+                         1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, (const uint8_t*)active,
+                         extra...);
   };
-  if (color) launch(k_integrate_pal4<true>);
-  else launch(k_integrate_pal4<false>);
+  if (ow) {
+    if (color) launch((k_integrate_pal4<true, true>), w);
+    else launch((k_integrate_pal4<false, true>), w);
+  } else if (color) launch(k_integrate_pal4<true>, NoObs{});
+  else launch(k_integrate_pal4<false>, NoObs{});
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+int ofx_integrate_palette_cull(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+                               const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
+                               const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
+                               const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
+                               double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                               float* tile_scratch, uint8_t* active, ofx_stream_t s) {
+  return integrate_cull_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                             pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, tile_scratch,
+                             active, nullptr, s);
+}
+
+int ofx_integrate_palette_cull_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+                                 const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
+                                 const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
+                                 const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
+                                 double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                                 float* tile_scratch, uint8_t* active, const ofx_obs_weights* ow, ofx_stream_t s) {
+  OFX_CHECK_ARG(ow, "null observation weights");
+  return integrate_cull_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                             pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, tile_scratch,
+                             active, ow, s);
+}
+
+static int integrate_points_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
+                                 const float* color_im, const float* points, const int64_t* voxel_ids,
+                                 const uint8_t* valid, int64_t n_points, double obs_weight, float* tsdf, float* weight,
+                                 float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
+  BrickGeom g;
+  int st = make_geom(desc, &g);
+  if (st) return st;
+  if (ow && (st = check_obs(desc, ow))) return st;
+  OFX_CHECK_ARG(cam && depth && tsdf && weight && n_points >= 0, "null buffer / bad size");
+  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
+  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
+  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
+  if (n_points == 0) return OFX_OK;
+  OFX_CHECK_ARG(points && voxel_ids, "null points / voxel ids");
+  if (ow)
+    hipLaunchKernelGGL((k_integrate_points<false, true>), dim3(grid_for(n_points, 256, 1 << 30)), dim3(256), 0, as_stream(s), g,
+                       make_cam(cam), depth, color_im, points, voxel_ids, valid, n_points, desc->trunc_margin,
+                       1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, ObsW{ow->obs_im, ow->w_max});
+  else
+    hipLaunchKernelGGL(desc->semantics == OFX_SEM_PYCUDA ? (k_integrate_points<true>) : (k_integrate_points<false>),
+                     dim3(grid_for(n_points, 256, 1 << 30)), dim3(256), 0, as_stream(s), g, make_cam(cam), depth,
+                     color_im, points, voxel_ids, valid, n_points, desc->trunc_margin, 1.0 / desc->trunc_margin,
+                     obs_weight, tsdf, weight, color, n_updated, NoObs{});
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
@@ -1063,21 +1271,17 @@ int ofx_integrate_points(const ofx_volume_desc* desc, const ofx_camera* cam, con
                          const float* points, const int64_t* voxel_ids, const uint8_t* valid, int64_t n_points,
                          double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                          ofx_stream_t s) {
-  BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  OFX_CHECK_ARG(cam && depth && tsdf && weight && n_points >= 0, "null buffer / bad size");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
-  if (n_points == 0) return OFX_OK;
-  OFX_CHECK_ARG(points && voxel_ids, "null points / voxel ids");
-  hipLaunchKernelGGL(desc->semantics == OFX_SEM_PYCUDA ? (k_integrate_points<true>) : (k_integrate_points<false>),
-                     dim3(grid_for(n_points, 256, 1 << 30)), dim3(256), 0, as_stream(s), g, make_cam(cam), depth,
-                     color_im, points, voxel_ids, valid, n_points, desc->trunc_margin, 1.0 / desc->trunc_margin,
-                     obs_weight, tsdf, weight, color, n_updated);
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  return integrate_points_impl(desc, cam, depth, color_im, points, voxel_ids, valid, n_points, obs_weight, tsdf, weight,
+                               color, n_updated, nullptr, s);
+}
+
+int ofx_integrate_points_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                           const float* points, const int64_t* voxel_ids, const uint8_t* valid, int64_t n_points,
+                           double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                           const ofx_obs_weights* ow, ofx_stream_t s) {
+  OFX_CHECK_ARG(ow, "null observation weights");
+  return integrate_points_impl(desc, cam, depth, color_im, points, voxel_ids, valid, n_points, obs_weight, tsdf, weight,
+                               color, n_updated, ow, s);
 }
 
 int ofx_deform_points(const float* points, int64_t n_points, const int32_t* anchors, const float* weights,

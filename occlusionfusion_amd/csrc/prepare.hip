@@ -112,6 +112,39 @@ __global__ __launch_bounds__(256) void k_prepare_normals(const float* __restrict
   nimg[2 * hw + p] = nz;
 }
 
+// Observation weights of the weighted integrate (ofx_observation_weights; ofx.h spells the arithmetic out): one thread per
+// pixel over the vertex and normal maps just written (L2-resident), six coalesced planar loads and one store. COSP is
+// the angle term's power (0, 1 or 2: no powf).
+template <int COSP>
+__global__ __launch_bounds__(256) void k_observation_weights(const float* __restrict__ pimg, const float* __restrict__ nimg,
+                                                              int64_t hw, float z_ref, float w_floor, float edge_weight,
+                                                              float* __restrict__ obs) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= hw) return;
+  const float px = pimg[p], py = pimg[hw + p], pz = pimg[2 * hw + p];
+  const float nx = nimg[p], ny = nimg[hw + p], nz = nimg[2 * hw + p];
+  float w;
+  if (!(pz > 0.f)) {
+    w = 0.f;
+  } else if (nx == 0.f && ny == 0.f && nz == 0.f) {
+    w = edge_weight;
+  } else {
+    const float dot = (nx * px + ny * py) + nz * pz;
+    const float ss = (px * px + py * py) + pz * pz;
+    float c = cdiv(-dot, (float)sqrt((double)ss));
+    if (!(c > 0.f)) c = 0.f;   // (a NaN too)
+    if (c > 1.f) c = 1.f;
+    const float a = COSP == 0 ? 1.f : COSP == 1 ? c : c * c;
+    float sc = 1.f;
+    if (z_ref != 0.f) {
+      const float r = cdiv(z_ref, pz);
+      sc = fminf(1.f, r * r);
+    }
+    w = fmaxf(w_floor, a * sc);
+  }
+  obs[p] = w;
+}
+
 }  // namespace ofx
 
 using namespace ofx;
@@ -151,6 +184,34 @@ int ofx_prepare_depth(const void* depth, int32_t is_u16, int32_t height, int32_t
   if (normal_image)
     hipLaunchKernelGGL(k_prepare_normals, dim3(grid_for((int64_t)height * width, 256, 1 << 30)), dim3(256), 0, hs,
                        (const float*)point_image, height, width, prm->edge_max, normal_image);
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+int ofx_observation_weights(const float* point_image, const float* normal_image, int32_t height, int32_t width,
+                            const ofx_obs_params* prm, float* obs_im, ofx_stream_t s) {
+  OFX_CHECK_ARG(prm, "null params");
+  OFX_CHECK_ARG(prm->cos_power >= 0 && prm->cos_power <= 2, "cos_power %d outside {0, 1, 2}", prm->cos_power);
+  OFX_CHECK_ARG(prm->z_ref >= 0.f && std::isfinite(prm->z_ref), "z_ref (%g) must be finite and >= 0", (double)prm->z_ref);
+  OFX_CHECK_ARG(prm->w_floor >= 0.f && std::isfinite(prm->w_floor), "w_floor (%g) must be finite and >= 0",
+                (double)prm->w_floor);
+  OFX_CHECK_ARG(prm->edge_weight >= 0.f && std::isfinite(prm->edge_weight), "edge_weight (%g) must be finite and >= 0",
+                (double)prm->edge_weight);
+  OFX_CHECK_ARG(height >= 1 && width >= 1 && (int64_t)height * width < ((int64_t)1 << 31), "bad image size %d x %d", width,
+                height);
+  OFX_CHECK_ARG(point_image && normal_image && obs_im, "null buffer");
+  OFX_CHECK_ARG(((reinterpret_cast<uintptr_t>(point_image) | reinterpret_cast<uintptr_t>(normal_image) |
+                  reinterpret_cast<uintptr_t>(obs_im)) & 3) == 0, "buffers must be 4-byte aligned");
+  const int64_t hw = (int64_t)height * width;
+  const dim3 grid(grid_for(hw, 256, 1 << 30));
+  hipStream_t hs = as_stream(s);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, hs, point_image, normal_image, hw, prm->z_ref, prm->w_floor,
+                       prm->edge_weight, obs_im);
+  };
+  if (prm->cos_power == 0) go(k_observation_weights<0>);
+  else if (prm->cos_power == 1) go(k_observation_weights<1>);
+  else go(k_observation_weights<2>);
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }

@@ -128,6 +128,96 @@ def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin
     return None
 
 
+# --------------------------------------------------------------------------------------------- weighted integrate
+def _obs_weights(obs_im, depth, w_max):
+    if obs_im.dtype != torch.float32 or tuple(obs_im.shape) != tuple(depth.shape):
+        raise ValueError(f"weighted integrate: obs_im must be float32 of the depth's shape {tuple(depth.shape)}, got "
+                         f"{obs_im.dtype} {tuple(obs_im.shape)}")
+    if not obs_im.is_contiguous():
+        raise ValueError("weighted integrate: obs_im must be contiguous")
+    return _lib.ObsWeights(obs_im.data_ptr(), float(w_max), 0.0)
+
+
+@_op("integrate_weighted", mutates_args=("tsdf", "weight", "color", "n_updated"))
+def integrate_weighted(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], n_updated: Optional[Tensor], depth: Tensor,
+                       color_im: Optional[Tensor], dims: List[int], brick_range: List[int], origin: List[float],
+                       voxel_size: float, trunc_margin: float, semantics: int, intr: List[float], obs_weight: float,
+                       packed_nodes: Optional[Tensor], n_nodes: int, k: int, brick_list: Optional[Tensor], n_list: int,
+                       anchors: Optional[Tensor], weights: Optional[Tensor], pal_ids: Optional[Tensor],
+                       pal_n: Optional[Tensor], local: Optional[Tensor], obs_im: Tensor, w_max: float) -> None:
+    """torch.ops.ofx.integrate with a per-pixel observation-weight image obs_im (f32, the depth's shape) and a cap w_max
+    on the stored weight (inf: none): ofx_integrate_w / ofx_integrate_palette_w (new capability, CPU semantics only; off
+    by default — nothing calls it unless a weight image or a cap is asked for)."""
+    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
+    cam = _camera(intr, depth.shape[0], depth.shape[1])
+    ow = _obs_weights(obs_im, depth, w_max)
+    s = _stream(tsdf)
+    if packed_nodes is None:
+        call("ofx_integrate_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), 0, None, 0, 1, ptr(brick_list),
+             n_list, None, None, float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), byref(ow), s)
+    elif pal_ids is not None:
+        call("ofx_integrate_palette_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), ptr(packed_nodes), n_nodes, k,
+             ptr(brick_list), n_list, ptr(anchors), ptr(weights), ptr(pal_ids), ptr(pal_n), ptr(local),
+             float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), byref(ow), s)
+    else:
+        call("ofx_integrate_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), 1, ptr(packed_nodes), n_nodes, k,
+             ptr(brick_list), n_list, ptr(anchors), ptr(weights), float(obs_weight), ptr(tsdf), ptr(weight),
+             ptr(color), ptr(n_updated), byref(ow), s)
+
+
+@integrate_weighted.register_fake
+def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics,
+      intr, obs_weight, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights, pal_ids, pal_n, local, obs_im,
+      w_max):
+    return None
+
+
+@_op("integrate_points_weighted", mutates_args=("tsdf", "weight", "color", "n_updated"))
+def integrate_points_weighted(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], n_updated: Optional[Tensor],
+                              depth: Tensor, color_im: Optional[Tensor], dims: List[int], brick_range: List[int],
+                              origin: List[float], voxel_size: float, trunc_margin: float, semantics: int,
+                              intr: List[float], obs_weight: float, points: Tensor, voxel_ids: Tensor,
+                              valid: Optional[Tensor], obs_im: Tensor, w_max: float) -> None:
+    """torch.ops.ofx.integrate_points with an observation-weight image and a weight cap (ofx_integrate_points_w)."""
+    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
+    cam = _camera(intr, depth.shape[0], depth.shape[1])
+    ow = _obs_weights(obs_im, depth, w_max)
+    call("ofx_integrate_points_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), ptr(points), ptr(voxel_ids),
+         ptr(valid), points.shape[0], float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), byref(ow),
+         _stream(tsdf))
+
+
+@integrate_points_weighted.register_fake
+def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics,
+      intr, obs_weight, points, voxel_ids, valid, obs_im, w_max):
+    return None
+
+
+@_op("observation_weights", mutates_args=())
+def observation_weights(point_image: Tensor, normal_image: Tensor, cos_power: int, z_ref: float, w_floor: float,
+                        edge_weight: float) -> Tensor:
+    """ofx_observation_weights (new capability, no reference twin): the per-pixel observation weight (H,W) f32 of a frame
+    from ofx_prepare_depth's vertex map and normal map, (3,H,W) f32 each — an angle term cos^cos_power of the normal
+    against the viewing ray, a range term min(1, (z_ref / z)^2) (z_ref = 0: none), floored at w_floor; edge_weight where
+    a pixel has depth but no normal, 0 at holes."""
+    if point_image.dim() != 3 or point_image.shape[0] != 3 or tuple(normal_image.shape) != tuple(point_image.shape):
+        raise ValueError(f"observation_weights: point_image and normal_image must both be (3, H, W), got "
+                         f"{tuple(point_image.shape)} and {tuple(normal_image.shape)}")
+    if point_image.dtype != torch.float32 or normal_image.dtype != torch.float32:
+        raise ValueError("observation_weights: point_image and normal_image must be float32")
+    p, n = point_image.contiguous(), normal_image.contiguous()
+    H, W = int(p.shape[1]), int(p.shape[2])
+    prm = _lib.ObsParams(int(cos_power), float(z_ref), float(w_floor), float(edge_weight))
+    out = torch.empty((H, W), dtype=torch.float32, device=p.device)
+    call("ofx_observation_weights", ptr(p), ptr(n), H, W, byref(prm), ptr(out), _stream(p))
+    return out
+
+
+@observation_weights.register_fake
+def _(point_image, normal_image, cos_power, z_ref, w_floor, edge_weight):
+    return point_image.new_empty((point_image.shape[1], point_image.shape[2]), dtype=torch.float32)
+
+
 @_op("raycast", mutates_args=())
 def raycast(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], dims: List[int], origin: List[float],
             voxel_size: float, trunc_margin: float, intr: List[float], height: int, width: int, z_near: float,
@@ -681,4 +771,5 @@ def _(state, handle, match_weights, kernel, scale):
 
 OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
-       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate", "gn_set_robust")
+       "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate", "gn_set_robust",
+       "integrate_weighted", "integrate_points_weighted", "observation_weights")

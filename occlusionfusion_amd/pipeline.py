@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .registration import GaussNewtonSolver
-from .tsdf import TSDFVolume
+from .tsdf import TSDFVolume, fusion_weight_params, resolve_w_min
 from .warpfield import EDGraph, WarpField
 
 
@@ -32,7 +32,14 @@ class FrameInputs:
 
 class FusionPipeline:
     def __init__(self, seq, origin, voxel_size, dims, n_matches=10000, device=None, shard=None, gn_params=None,
-                 with_color=True, overlap=False):
+                 with_color=True, overlap=False, fusion_weights=None):
+        """fusion_weights (None / True / a dict of cos_power, z_ref, w_floor, edge_weight, max_weight, filter): every
+        frame is fused with per-pixel observation weights and, with max_weight, a cap on the accumulated weight
+        (TSDFVolume.integrate_device's weighted form; tsdf.FUSION_WEIGHT_DEFAULTS). The map is built where the frame is
+        staged, from the vertex and normal maps of the filtered frame (filter: what depth_filter takes, default True);
+        the integrated depth stays the raw frame. None (the default) is the reference's plain running average: the
+        calls made are the ones made without this keyword."""
+        self.fusion_weights = fusion_weight_params(fusion_weights)   # (TypeError / ValueError before any device work)
         self.seq = seq
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         cam = seq.cam
@@ -40,6 +47,7 @@ class FusionPipeline:
         self.fopt = SimpleNamespace(source_frame=0, skip_rate=1)
         self.vol = TSDFVolume.from_grid(origin, voxel_size, dims, self.intr, self.fopt, device=self.device, shard=shard)
         self.vol.with_color = with_color
+        self.vol.fusion_weights = self.fusion_weights
         self.graph = EDGraph(seq.nodes, seq.edges, seq.edge_weights, node_coverage=seq.node_coverage)
         self.wf = WarpField(self.graph, self.vol)
         self.nodes_t = torch.from_numpy(seq.nodes).to(self.device)
@@ -106,6 +114,7 @@ class FusionPipeline:
         """GN solve of frame fi; next_fi: the next frame, whose solver setup is prefetched concurrently. Frame fi's
         depth/colour unpacking for its integrate is enqueued first (TSDFVolume.stage), so the host work between the
         solve's return and the integrate launch is only the integrate's own."""
+        self.vol.fusion_weights = self.fusion_weights
         self.vol.stage(fi.im)
         out = self.solver.optimize(self.nodes_t, self.edges_t, self.ew_t, fi.tpos, fi.conf, fi.src, fi.anchors,
                                    fi.weights, fi.tgt, self.intr, prev_rot=self.prev_rot, prev_trans=self.prev_trans,
@@ -171,10 +180,12 @@ class FusionPipeline:
         self.integrate(fi, t, count_updates)
         return self.last
 
-    def sample_model(self, max_model_points, w_min=1.0):
+    def sample_model(self, max_model_points, w_min=None):
         """(Re)sample the volume model on torch's current stream (WarpField.surface_points, sync=False: no host read):
         max_model_points padded rows and their valid mask. model_counts keeps a device copy of every sampling's
-        [accepted, emitted] (read them at the end of a run, not per frame)."""
+        [accepted, emitted] (read them at the end of a run, not per frame). w_min (accumulated weight) None: 1.0, or the
+        fusion weights' w_floor when the volume fuses with them (tsdf.resolve_w_min)."""
+        w_min = resolve_w_min(w_min, self.vol.fusion_weights)
         m = self.wf.surface_points(int(max_model_points), w_min, sync=False)
         self._vmodel = m
         self.model_counts.append(m["count"].clone())
@@ -204,13 +215,14 @@ class FusionPipeline:
             splat_radius = default_splat_radius(self.vol._voxel_size, with_normals)
         return dict(occlusion=True, renderer=self._renderer, splat_radius=splat_radius, occl_margin=occl_margin)
 
-    def grow_graph(self, max_model_points=65536, w_min=1.0, resample=False, **grow):
+    def grow_graph(self, max_model_points=65536, w_min=None, resample=False, **grow):
         """Grow the graph from the fused volume (WarpField.grow_from_volume; **grow: its keywords) under the transforms
         of the last integrated frame, and let the loop follow: the graph tensors and the previous transforms get the new
         rows, the solver is replaced by a larger one with the same parameters when the graph outgrows it, and the volume
         model is sampled again, because skins changed (resample=True: also when no node was added — the loop's frames that
         left the sampling after their integrate to this call). One host read (the counts). -> grow_from_volume's dict."""
         M = int(max_model_points)
+        w_min = resolve_w_min(w_min, self.vol.fusion_weights)   # (None: 1.0, or the fusion weights' w_floor)
         grow.setdefault("max_points", M)
         grow.setdefault("w_min", w_min)
         self.flush()
@@ -243,9 +255,11 @@ class FusionPipeline:
         return tpos, conf
 
     def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
-                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None, photo=None, robust=None):
+                      occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None, photo=None, robust=None,
+                      fusion=None):
         from .association import ProjectiveAssociator, icp_track, photo_params
         M = int(max_model_points)
+        self.vol.fusion_weights = fusion   # (the frame staged and integrated below is fused with these, or plainly)
         if getattr(self, "_vassoc", None) is None or self._vassoc.max_points < M:
             self._vassoc = ProjectiveAssociator(M, self.device)
         if getattr(self, "_vmodel", None) is None or self._vmodel["points"].shape[0] != M:
@@ -293,8 +307,9 @@ class FusionPipeline:
         return out
 
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
-                   max_model_points=65536, w_min=1.0, rigid_iters=0, occlusion=False, splat_radius=None,
-                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, robust=None, **assoc):
+                   max_model_points=65536, w_min=None, rigid_iters=0, occlusion=False, splat_radius=None,
+                   occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, robust=None,
+                   fusion_weights=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -341,17 +356,26 @@ class FusionPipeline:
         `mode` is ignored then: the target is always the vertex. None leaves the loop as it is.
 
         robust (both models; None / "huber" / "tukey" / {"kernel", "scale"}): every solve of the tracking loop runs with
-        that robust kernel on its data rows (GaussNewtonSolver.optimize's robust=). None leaves the loop as it is."""
+        that robust kernel on its data rows (GaussNewtonSolver.optimize's robust=). None leaves the loop as it is.
+
+        fusion_weights (both models; None / True / a dict, as the constructor takes it; None: the constructor's): the
+        frame this call integrates is fused with per-pixel observation weights (and the weight cap max_weight). Its map
+        is built where the frame is staged, ahead of the solve, from the filtered frame's vertex and normal maps
+        (`filter`; not shared with depth_filter's own ofx_prepare_depth call), and an overlapped integrate gets it with
+        the depth and the colour. w_min=None is 1.0 without fusion weights and their w_floor with them (fractional
+        weights: 1.0 would empty the sampled model after the source frame); max_weight must not lie below it."""
         from .association import photo_params
         from .registration import robust_params
         photo_params(photo)   # (an unknown key is a TypeError before anything is touched)
         robust_params(robust)
+        fw = fusion_weight_params(fusion_weights) if fusion_weights is not None else getattr(self, "fusion_weights", None)
+        w_min = resolve_w_min(w_min, fw)   # (a ValueError for a cap below it, before any device work)
         if grow_every and model != "volume":
             raise ValueError("grow_every needs model='volume': the graph grows from the fused volume")
         if model == "volume":
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
                                       assoc, (occlusion, splat_radius, occl_margin), depth_filter, grow_every, grow,
-                                      photo, robust)
+                                      photo, robust, fw)
         if model != "canonical":
             raise ValueError(f"model must be 'canonical' or 'volume', got {model!r}")
         from .association import ProjectiveAssociator, icp_track
@@ -367,6 +391,7 @@ class FusionPipeline:
             self._track = (pts, a, w, v, ProjectiveAssociator(pts.shape[0], self.device))
         pts, a, w, v, assoc_h = self._track
         assoc.setdefault("max_matches", self.n_matches)
+        self.vol.fusion_weights = fw
         self.vol.stage(fi.im)
         out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
                                 fi.im[-1], self.intr, self.prev_rot, self.prev_trans,

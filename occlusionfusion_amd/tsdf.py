@@ -26,6 +26,90 @@ TRUNC_MARGIN = 0.04  # tsdf.py:127
 SEMANTICS = {"cpu": 0, "pycuda": 1}   # OFX_SEM_CPU / OFX_SEM_PYCUDA
 
 
+# fusion_weights=True: the per-pixel observation weights of the weighted integrate. Conventions of volumetric fusion
+# (an angle term cos^2, a range term against 1 m, a small floor, depth-edge pixels left out), not measurements.
+FUSION_WEIGHT_DEFAULTS = dict(cos_power=2, z_ref=1.0, w_floor=0.05, edge_weight=0.0, max_weight=None, filter=True)
+FUSION_EDGE_MAX = 0.03   # the normal map's depth-edge bound (prepare_depth_device's default, the association's)
+
+
+def _finite_nonneg(name, v):
+    v = float(v)
+    if not (np.isfinite(v) and v >= 0.0):
+        raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+    return v
+
+
+def observation_weight_params(cos_power=2, z_ref=1.0, w_floor=0.05, edge_weight=0.0):
+    """The checked parameters of TSDFVolume.observation_weights (a ValueError for a bad value, no device work)."""
+    if isinstance(cos_power, bool) or cos_power not in (0, 1, 2):
+        raise ValueError(f"cos_power must be 0, 1 or 2, got {cos_power!r}")
+    return dict(cos_power=int(cos_power), z_ref=_finite_nonneg("z_ref", z_ref), w_floor=_finite_nonneg("w_floor", w_floor),
+                edge_weight=_finite_nonneg("edge_weight", edge_weight))
+
+
+def max_weight_param(max_weight):
+    """max_weight=None -> +inf (no cap); else a float > 0 (a ValueError otherwise)."""
+    if max_weight is None:
+        return float("inf")
+    m = float(max_weight)
+    if not m > 0.0:
+        raise ValueError(f"max_weight must be > 0 (None: no cap), got {max_weight!r}")
+    return m
+
+
+def fusion_weight_params(fusion_weights):
+    """fusion_weights=None | False -> None; True -> FUSION_WEIGHT_DEFAULTS; a dict -> the defaults with its entries. An
+    unknown key is a TypeError and a bad value a ValueError, both before any device work. `filter` takes what
+    depth_filter takes (None / False: the raw frame's normals; True; a dict of radius, sigma_s, sigma_r, range_cut) and
+    comes back as prepare_depth_device's keywords."""
+    from .image_proc import PREPARE_DEFAULTS
+    if fusion_weights is None or fusion_weights is False:
+        return None
+    prm = dict(FUSION_WEIGHT_DEFAULTS)
+    if fusion_weights is not True:
+        if not isinstance(fusion_weights, dict):
+            raise TypeError(f"fusion_weights must be None, True or a dict, got {type(fusion_weights).__name__}")
+        unknown = set(fusion_weights) - set(prm)
+        if unknown:
+            raise TypeError(f"unknown fusion_weights parameters {sorted(unknown)}")
+        prm.update(fusion_weights)
+    out = observation_weight_params(prm["cos_power"], prm["z_ref"], prm["w_floor"], prm["edge_weight"])
+    out["max_weight"] = max_weight_param(prm["max_weight"])
+    f = prm["filter"]
+    if f is None or f is False:
+        filt = dict(PREPARE_DEFAULTS, radius=0)
+    else:
+        filt = dict(PREPARE_DEFAULTS)
+        if f is not True:
+            if not isinstance(f, dict):
+                raise TypeError(f"fusion_weights filter must be None, True or a dict, got {type(f).__name__}")
+            unknown = set(f) - set(filt)
+            if unknown:
+                raise TypeError(f"unknown fusion_weights filter parameters {sorted(unknown)}")
+            filt.update(f)
+        if not (isinstance(filt["radius"], (int, np.integer)) and 0 <= filt["radius"] <= _lib.PREPARE_RMAX):
+            raise ValueError(f"fusion_weights filter radius must be an integer in [0, {_lib.PREPARE_RMAX}]")
+        if not (float(filt["sigma_s"]) > 0 and float(filt["sigma_r"]) > 0):
+            raise ValueError("fusion_weights filter sigma_s and sigma_r must be positive")
+        if filt["range_cut"] is not None and not float(filt["range_cut"]) > 0:
+            raise ValueError("fusion_weights filter range_cut must be positive")
+    out["filter"] = filt
+    return out
+
+
+def resolve_w_min(w_min, fusion):
+    """The model sampling's w_min (accumulated weight): None -> 1.0 without fusion weights (one whole observation), the
+    weights' w_floor with them (seen at least once by a pixel that has a normal; 1.0 would empty the model after the
+    source frame). An explicit value stands. The weight cap must not lie below it (ValueError)."""
+    if w_min is None:
+        w_min = 1.0 if fusion is None else fusion["w_floor"]
+    w_min = float(w_min)
+    if fusion is not None and fusion["max_weight"] < w_min:
+        raise ValueError(f"fusion_weights max_weight ({fusion['max_weight']}) is below the model's w_min ({w_min}): no "
+                         "voxel could ever be sampled")
+    return w_min
+
+
 def _opt(fopt, name, default=None):
     if fopt is None:
         return default
@@ -135,6 +219,12 @@ class TSDFVolume:
         # voxels provably update nothing are skipped; bit-identical results
         self.brick_cull = True
         self._cull = None          # (tile maxima, per-slot flags) scratch of the cull
+        # fusion_weight_params(...) or None: with it every staged / updated frame gets an observation-weight map
+        # (obs_t) and integrate_device() fuses with it; None (the default) is the reference's plain running average
+        self.fusion_weights = None
+        self.obs_t = None          # the current frame's observation-weight map (H,W) f32, and its weight cap
+        self.obs_wmax = float("inf")
+        self._ones = None          # a constant-1 weight image: a cap without a weight image
         call("ofx_volume_reset", byref(self.desc), ptr(self.tsdf_b), ptr(self.weight_b), ptr(self.color_b), stream_ptr())
         self.warpfield = None
         self._world_pts = None
@@ -158,23 +248,45 @@ class TSDFVolume:
         color = torch.empty((H, W), dtype=torch.float32, device=self.device)
         rgb = im_t[:3].contiguous()
         call("ofx_pack_color", ptr(rgb), H, W, ptr(color), stream_ptr())
-        return depth, color
+        fw = self.fusion_weights
+        if fw is None:
+            return depth, color
+        # the frame's observation weights, from the vertex and normal maps of the (filtered) frame; the integrated
+        # depth stays the raw one. Holes stay holes under the filter: no pixel with raw depth gets a hole's weight 0.
+        from .image_proc import prepare_depth_device
+        K = self.cam_intr
+        prep = prepare_depth_device(depth, K[0, 0], K[1, 1], K[0, 2], K[1, 2], edge_max=FUSION_EDGE_MAX, **fw["filter"])
+        obs = torch.ops.ofx.observation_weights(prep["point_image"], prep["normals"], fw["cos_power"], fw["z_ref"],
+                                                fw["w_floor"], fw["edge_weight"])
+        return depth, color, obs, fw["max_weight"]
+
+    def observation_weights(self, point_image, normal_image, cos_power=2, z_ref=1.0, w_floor=0.05, edge_weight=0.0):
+        """The per-pixel observation weights (H,W) f32 of a frame for integrate(weight_image=), from
+        prepare_depth_device's vertex map and normal map (3,H,W) (torch.ops.ofx.observation_weights ->
+        ofx_observation_weights; new capability, no reference twin): max(w_floor, cos^cos_power · min(1, (z_ref/z)²))
+        with cos the angle between the normal and the viewing ray (cos_power 0, 1 or 2; z_ref = 0: no range term),
+        edge_weight where a pixel has depth but no normal (border, beside a hole, on a depth edge), 0 at holes. The
+        defaults are conventions of volumetric fusion, not measurements. No host sync."""
+        prm = observation_weight_params(cos_power, z_ref, w_floor, edge_weight)
+        p = torch.as_tensor(point_image, dtype=torch.float32, device=self.device)
+        n = torch.as_tensor(normal_image, dtype=torch.float32, device=self.device)
+        return torch.ops.ofx.observation_weights(p, n, prm["cos_power"], prm["z_ref"], prm["w_floor"], prm["edge_weight"])
 
     def stage(self, im):
         """Unpack the frame that the next update(im, ...) will take, now: its device work (the colour packing) is
         enqueued at this point of the stream and update() only adopts the result. A frame loop stages frame t
         before frame t's solve, so the host work between the solve's return and the integrate launch shrinks (the
-        GPU waits for it there)."""
+        GPU waits for it there). With fusion_weights set the frame's observation-weight map is built here too and
+        rides along (a fourth and fifth entry: the map and its weight cap)."""
         self._staged = (im,) + self._unpack(im)
 
     def update(self, im, frame_id):
         """tsdf.py:545-572: unpack the (6,H,W) frame; depth = im[-1]; colour folded on device."""
         st = getattr(self, "_staged", None)
         self._staged = None
-        if st is not None and st[0] is im:
-            self.depth_t, self.color_t = st[1], st[2]
-        else:
-            self.depth_t, self.color_t = self._unpack(im)
+        un = st[1:] if st is not None and st[0] is im else self._unpack(im)
+        self.depth_t, self.color_t = un[0], un[1]
+        self.obs_t, self.obs_wmax = (un[2], un[3]) if len(un) > 2 else (None, float("inf"))
         self.im = im
         if hasattr(self, "frame_id"):
             skip = _opt(self.fopt, "skip_rate", 1)
@@ -191,14 +303,49 @@ class TSDFVolume:
         return self.color_t.cpu().numpy()
 
     # ------------------------------------------------------------------ integrate
-    def integrate(self, image_data, obs_weight=1.):
-        """tsdf.py:378-494: warp (non-source frames) + integrate, fused on device."""
+    def integrate(self, image_data, obs_weight=1., weight_image=None, max_weight=None):
+        """tsdf.py:378-494: warp (non-source frames) + integrate, fused on device. weight_image / max_weight: the
+        weighted integrate (integrate_device)."""
+        self._check_weighted(weight_image, max_weight)
         self.update(image_data["im"], image_data["id"])
-        self.integrate_device(obs_weight)
+        self.integrate_device(obs_weight, weight_image=weight_image, max_weight=max_weight)
 
-    def integrate_device(self, obs_weight=1., count_updates=False):
+    def _check_weighted(self, weight_image, max_weight):
+        """The weighted integrate's arguments, checked before any device work -> (weighted?, w_max)."""
+        w_max = max_weight_param(max_weight)
+        on = weight_image is not None or max_weight is not None
+        if on and self.semantics != "cpu":
+            raise ValueError("the weighted integrate (weight_image / max_weight / fusion_weights) has 'cpu' semantics only")
+        return on, w_max
+
+    def _weight_image(self, weight_image):
+        """(H,W) f32 contiguous device tensor of the current frame's size: weight_image, or ones for a cap alone."""
+        H, W = (int(v) for v in self.depth_t.shape)
+        if weight_image is None:
+            if self._ones is None or tuple(self._ones.shape) != (H, W):
+                self._ones = torch.ones((H, W), dtype=torch.float32, device=self.device)
+            return self._ones
+        w = torch.as_tensor(weight_image, dtype=torch.float32, device=self.device).contiguous()
+        if tuple(w.shape) != (H, W):
+            raise ValueError(f"weight_image must have the depth image's shape {(H, W)}, got {tuple(w.shape)}")
+        return w
+
+    def integrate_device(self, obs_weight=1., count_updates=False, weight_image=None, max_weight=None):
         """Integrate the current (already updated) frame through torch.ops.ofx.integrate (the warped palette path:
-        its library call directly); no host sync."""
+        its library call directly); no host sync.
+
+        weight_image ((H,W) f32, e.g. observation_weights(...)) and / or max_weight: the weighted integrate (new; the
+        reference has none). A voxel's observation counts obs_weight · weight_image[its pixel] — a pixel whose weight
+        is not a finite number > 0 updates nothing — and the stored weight is capped at max_weight, so the model keeps
+        adapting. With both None, and no fusion_weights set on the volume, the calls are the unweighted ones, argument
+        for argument; with fusion_weights set, the map built when the frame was staged / updated is used."""
+        on, w_max = self._check_weighted(weight_image, max_weight)
+        if not on and self.obs_t is not None:
+            if self.semantics != "cpu":
+                raise ValueError("fusion_weights needs 'cpu' integrate semantics")
+            on, weight_image, w_max = True, self.obs_t, self.obs_wmax
+        if on:
+            return self._integrate_weighted(obs_weight, count_updates, self._weight_image(weight_image), w_max)
         src = _opt(self.fopt, "source_frame", 0)
         color = self.color_b if self.with_color else None
         color_im = self.color_t if self.with_color else None
@@ -238,10 +385,57 @@ class TSDFVolume:
                                 cache.anchors, cache.weights, cache.pal_ids if pal else None,
                                 cache.pal_n if pal else None, cache.local if pal else None)
 
-    def integrate_points(self, points, voxel_ids, valid=None, obs_weight=1., count_updates=False):
+    def _integrate_weighted(self, obs_weight, count_updates, wi, w_max):
+        """integrate_device's paths, one for one, through the _w entry points (the same kernels' weighted forms)."""
+        src = _opt(self.fopt, "source_frame", 0)
+        color = self.color_b if self.with_color else None
+        color_im = self.color_t if self.with_color else None
+        nu = self.n_updated if count_updates else None
+        d = self.desc
+        geo = ([int(v) for v in d.dim], [self.brick_x0, self.brick_x1], [float(v) for v in d.origin],
+               float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
+               [float(self.cam_intr[0, 0]), float(self.cam_intr[1, 1]), float(self.cam_intr[0, 2]),
+                float(self.cam_intr[1, 2])], float(obs_weight))
+        if self.frame_id == src:
+            ob = self.owned_bricks
+            torch.ops.ofx.integrate_weighted(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *geo,
+                                             None, 0, 1, ob, 0 if ob is None else int(ob.shape[0]), None, None, None,
+                                             None, None, wi, w_max)
+            return
+        if self.warpfield is None:
+            raise RuntimeError("non-source frame integrate needs tsdf.warpfield (WarpField) to be set")
+        cache = self.warpfield.skin_tsdf_cache()
+        nodes = self.warpfield.packed_nodes()
+        pal = self.use_palette and cache.pal_n is not None
+        if pal:
+            ow = _lib.ObsWeights(wi.data_ptr(), w_max, 0.0)
+            args = (byref(d), byref(self.camera()), ptr(self.depth_t), ptr(color_im), ptr(nodes),
+                    self.warpfield.num_nodes, cache.k, ptr(cache.brick_list), cache.n_list, ptr(cache.anchors),
+                    ptr(cache.weights), ptr(cache.pal_ids), ptr(cache.pal_n), ptr(cache.local), float(obs_weight),
+                    ptr(self.tsdf_b), ptr(self.weight_b), ptr(color), ptr(nu))
+            if self.brick_cull:
+                H, W = (int(v) for v in self.depth_t.shape)
+                nt = ((W + 7) // 8) * ((H + 7) // 8)
+                if self._cull is None or self._cull[0].numel() < nt or self._cull[1].numel() < cache.n_list:
+                    self._cull = (torch.empty(nt, dtype=torch.float32, device=self.device),
+                                  torch.empty(max(1, cache.n_list), dtype=torch.uint8, device=self.device))
+                call("ofx_integrate_palette_cull_w", *args, ptr(self._cull[0]), ptr(self._cull[1]), byref(ow),
+                     stream_ptr())
+            else:
+                call("ofx_integrate_palette_w", *args, byref(ow), stream_ptr())
+            return
+        torch.ops.ofx.integrate_weighted(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *geo,
+                                         nodes, self.warpfield.num_nodes, cache.k, cache.brick_list, cache.n_list,
+                                         cache.anchors, cache.weights, None, None, None, wi, w_max)
+
+    def integrate_points(self, points, voxel_ids, valid=None, obs_weight=1., count_updates=False, weight_image=None,
+                         max_weight=None):
         """tsdf.py:442-494 on explicit points: point p (already warped, e.g. WarpField.deform_tsdf) updates the
         voxel with C-order id voxel_ids[p] against the current frame (update() first). Voxel ids must be
-        distinct; ids outside this shard are ignored. Returns the update count (device u32 tensor) if asked."""
+        distinct; ids outside this shard are ignored. Returns the update count (device u32 tensor) if asked.
+        weight_image / max_weight: the weighted integrate, as integrate_device takes them (a fusion_weights map of
+        the volume is not applied here: explicit points come with explicit weights)."""
+        on, w_max = self._check_weighted(weight_image, max_weight)
         d = self.desc
         pts = torch.as_tensor(points, dtype=torch.float32, device=self.device).reshape(-1, 3).contiguous()
         vox = torch.as_tensor(voxel_ids, dtype=torch.int64, device=self.device).reshape(-1).contiguous()
@@ -249,6 +443,14 @@ class TSDFVolume:
             raise ValueError(f"{pts.shape[0]} points but {vox.shape[0]} voxel ids")
         v = None if valid is None else torch.as_tensor(valid, device=self.device).reshape(-1).to(torch.uint8)
         cnt = torch.zeros(1, dtype=torch.int32, device=self.device) if count_updates else None
+        if on:
+            torch.ops.ofx.integrate_points_weighted(
+                self.tsdf_b, self.weight_b, self.color_b if self.with_color else None, cnt, self.depth_t,
+                self.color_t if self.with_color else None, [int(x) for x in d.dim], [self.brick_x0, self.brick_x1],
+                [float(x) for x in d.origin], float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
+                [float(self.cam_intr[0, 0]), float(self.cam_intr[1, 1]), float(self.cam_intr[0, 2]),
+                 float(self.cam_intr[1, 2])], float(obs_weight), pts, vox, v, self._weight_image(weight_image), w_max)
+            return cnt
         torch.ops.ofx.integrate_points(
             self.tsdf_b, self.weight_b, self.color_b if self.with_color else None, cnt, self.depth_t,
             self.color_t if self.with_color else None, [int(x) for x in d.dim], [self.brick_x0, self.brick_x1],
