@@ -116,11 +116,6 @@ _SIGS = {
     "ofx_integrate_palette": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P],
     "ofx_integrate_palette_cull": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P,
                                    P, P],
-    "ofx_integrate_w": [P, P, P, P, c_int32, P, c_int32, c_int32, P, c_int32, P, P, c_double, P, P, P, P, P, P],
-    "ofx_integrate_points_w": [P, P, P, P, P, P, P, c_int64, c_double, P, P, P, P, P, P],
-    "ofx_integrate_palette_w": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P, P],
-    "ofx_integrate_palette_cull_w": [P, P, P, P, P, c_int32, c_int32, P, c_int32, P, P, P, P, P, c_double, P, P, P, P, P,
-                                     P, P, P],
     "ofx_observation_weights": [P, P, c_int32, c_int32, P, P, P],
     "ofx_deform_points": [P, c_int64, P, P, P, c_int32, P, c_int32, c_int32, P, P],
     "ofx_deform_points_lbs": [P, c_int64, P, P, P, c_int32, P, P, c_int32, P, P],
@@ -198,6 +193,9 @@ _SIGS = {
     "ofx_gn_set_idle_hook": [P, P, P],
     "ofx_gn_set_robust": [P, P],
 }
+# the weighted integrate: an entry point's arguments with the ofx_obs_weights pointer in front of the stream
+for _name in ("ofx_integrate", "ofx_integrate_points", "ofx_integrate_palette", "ofx_integrate_palette_cull"):
+    _SIGS[_name + "_w"] = _SIGS[_name][:-1] + [P, P]
 
 
 def _load():

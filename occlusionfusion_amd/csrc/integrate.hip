@@ -928,167 +928,201 @@ struct IntTimer {
     g_int_ev.emplace_back(e0, e1);
   }
 };
-#define OFX_TIMED_LAUNCH(T, kernel, grid, block, shm, stream, ...)                                         \
-  do {                                                                                                    \
-    if ((T).e0)                                                                                           \
-      hipExtLaunchKernelGGL(kernel, grid, block, shm, stream, (T).e0, (T).e1, 0, __VA_ARGS__);            \
-    else                                                                                                  \
-      hipLaunchKernelGGL(kernel, grid, block, shm, stream, __VA_ARGS__);                                  \
-  } while (0)
 
-// the weighted entry points' extra argument: checked, then handed to the kernels as ObsW
-int check_obs(const ofx_volume_desc* desc, const ofx_obs_weights* ow) {
-  OFX_CHECK_ARG(ow && ow->obs_im, "null observation weights");
+// Every launch of this file's integrate paths: 256 threads, no dynamic LDS; e0 / e1 (nullable) are recorded at the
+// kernel's start / end. (args convert to the kernel's parameter types: P is deduced from the kernel alone)
+template <typename T> struct as_is { using type = T; };
+template <typename... P>
+void launch(hipStream_t hs, hipEvent_t e0, hipEvent_t e1, void (*kernel)(P...), unsigned grid,
+            typename as_is<P>::type... args) {
+  if (e0 || e1)
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, hs, e0, e1, 0, args...);
+  else
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, hs, args...);
+}
+
+// two runtime flags -> template arguments: f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <typename F>
+void with_flags(bool a, bool b, F f) {
+  if (a) {
+    if (b) f(std::true_type{}, std::true_type{});
+    else f(std::true_type{}, std::false_type{});
+  } else if (b) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+// a kernel's last argument
+template <bool WT>
+obs_arg_t<WT> obs_of(const ObsW& w) {
+  if constexpr (WT) return w;
+  else return NoObs{};
+}
+
+// One call of ofx_integrate / _palette / _palette_cull or of a _w form (ow: null for the unweighted ones), in the
+// order of ofx_integrate_palette_cull_w's arguments; what an entry point does not have is null.
+struct IntCall {
+  const ofx_volume_desc* desc;
+  const ofx_camera* cam;
+  const float *depth, *color_im, *packed_nodes;
+  int32_t n_nodes, k;
+  const int32_t* brick_list;
+  int32_t n_list;
+  const uint16_t* anchors;
+  const float* weights;
+  const uint16_t* pal_ids;
+  const int32_t* pal_n;
+  const uint8_t* local_anchors;
+  double obs_weight;
+  float *tsdf, *weight, *color;
+  uint32_t* n_updated;
+  float* tile_scratch;
+  uint8_t* active;
+  const ofx_obs_weights* ow;
+  ofx_stream_t s;
+};
+
+// what every entry point checks first; bufs / bufs_msg: its own required pointers and sizes
+int check_frame(const ofx_volume_desc* desc, const ofx_camera* cam, bool bufs, const char* bufs_msg,
+                const float* color_im, const float* color, BrickGeom* g) {
+  int st = make_geom(desc, g);
+  if (st) return st;
+  OFX_CHECK_ARG(bufs, "%s", bufs_msg);
+  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
+  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
+  return OFX_OK;
+}
+
+int check_semantics(const ofx_volume_desc* desc) {
+  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
+  return OFX_OK;
+}
+
+// the weighted entry points' extra argument (null: the unweighted call): checked, then handed to the kernels as ObsW
+int check_obs(const ofx_volume_desc* desc, const ofx_obs_weights* ow, ObsW* w) {
+  if (!ow) return OFX_OK;
+  OFX_CHECK_ARG(ow->obs_im, "null observation weights");
   OFX_CHECK_ARG((reinterpret_cast<uintptr_t>(ow->obs_im) & 3) == 0, "obs_im must be 4-byte aligned");
   OFX_CHECK_ARG(ow->w_max > 0.f, "w_max (%g) must be > 0 (+inf: no cap)", (double)ow->w_max);
   OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU, "the weighted integrate has CPU semantics only (semantics %d)",
                 desc->semantics);
+  *w = ObsW{ow->obs_im, ow->w_max};
   return OFX_OK;
 }
 
-// The bodies of ofx_integrate* and their _w twins: ow == nullptr launches exactly what the unweighted entry points
-// always launched; with ow the WT instantiation of the same kernel runs.
-int integrate_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
-                   int32_t warp, const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
-                   int32_t n_list, const uint16_t* anchors, const float* weights, double obs_weight, float* tsdf,
-                   float* weight, float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
+// The specialised kernels (k_integrate_src, k_integrate_pal4) serve CPU semantics and 32-bit voxel offsets; the
+// environment is read at every call (OFX_INT_GENERIC: the generic kernel, for A/B runs).
+bool fast_path(const ofx_volume_desc* desc, const BrickGeom& g) {
+  return desc->semantics == OFX_SEM_CPU && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC");
+}
+
+// k_integrate over nb bricks: the source frame (WARP false: no nodes, K = 1), global anchors, or the palette (PAL)
+template <bool WARP, bool PAL>
+void launch_generic(const IntCall& a, const BrickGeom& g, const CamD& c, const ObsW& w, unsigned nb, hipEvent_t e0,
+                    hipEvent_t e1) {
+  with_flags(a.desc->semantics == OFX_SEM_PYCUDA, a.ow != nullptr, [&](auto PYC, auto WT) {
+    if constexpr (!(PYC() && WT()))   // check_obs refuses the pair: that kernel does not exist
+      launch(as_stream(a.s), e0, e1, k_integrate<WARP, PAL, PYC(), WT()>, nb, g, c, a.depth, a.color_im,
+             WARP ? (const float4*)a.packed_nodes : nullptr, WARP ? a.k : 1, a.brick_list,
+             WARP ? (const ushort4*)a.anchors : nullptr, WARP ? (const float4*)a.weights : nullptr, a.pal_ids, a.pal_n,
+             (const uchar4*)a.local_anchors, a.desc->trunc_margin, a.obs_weight, a.tsdf, a.weight, a.color, a.n_updated,
+             obs_of<WT()>(w));
+  });
+}
+
+// ofx_integrate and ofx_integrate_w: the source frame (warp == 0) or global anchors
+int integrate_impl(const IntCall& a, int32_t warp) {
   BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  OFX_CHECK_ARG(cam && depth && tsdf && weight, "null buffer");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  CamD c = make_cam(cam);
-  hipStream_t hs = as_stream(s);
-  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
-  const bool pyc = desc->semantics == OFX_SEM_PYCUDA;
   ObsW w{};
-  if (ow) {
-    if ((st = check_obs(desc, ow))) return st;
-    w = ObsW{ow->obs_im, ow->w_max};
-  }
-  if (!warp && !pyc && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC")) {
-    const unsigned nb = brick_list ? (unsigned)n_list : (unsigned)g.n_bricks;
-    if (nb == 0) return OFX_OK;
-    if (ow) {
-      if (color)
-        hipLaunchKernelGGL((k_integrate_src<true, true>), dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
-                           brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
-                           n_updated, w);
-      else
-        hipLaunchKernelGGL((k_integrate_src<false, true>), dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
-                           brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
-                           n_updated, w);
-    } else if (color)
-      hipLaunchKernelGGL(k_integrate_src<true>, dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
-                         brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
-                         n_updated, NoObs{});
-    else
-      hipLaunchKernelGGL(k_integrate_src<false>, dim3(nb), dim3(256), 0, hs, g, make_div(g), c, depth, color_im,
-                         brick_list, desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color,
-                         n_updated, NoObs{});
-  } else if (!warp) {
-    // generic source-frame form: pycuda semantics, shards of >= 2^31 voxels, or the OFX_INT_GENERIC A/B; a brick
-    // list (hash shard) is walked as in the warped form
-    OFX_CHECK_ARG(brick_list == nullptr || (n_list >= 0 && n_list <= g.n_bricks), "bad n_list");
-    const unsigned nb = brick_list ? (unsigned)n_list : (unsigned)g.n_bricks;
-    if (nb == 0) return OFX_OK;
-    if (ow)
-      hipLaunchKernelGGL((k_integrate<false, false, false, true>), dim3(nb), dim3(256), 0, hs, g, c, depth, color_im,
-                         (const float4*)nullptr, 1, brick_list, (const ushort4*)nullptr, (const float4*)nullptr,
-                         (const uint16_t*)nullptr, (const int32_t*)nullptr, (const uchar4*)nullptr, desc->trunc_margin,
-                         obs_weight, tsdf, weight, color, n_updated, w);
-    else
-      hipLaunchKernelGGL(pyc ? (k_integrate<false, false, true>) : (k_integrate<false, false, false>),
-                         dim3(nb), dim3(256), 0, hs, g, c, depth,
-                         color_im, (const float4*)nullptr, 1, brick_list, (const ushort4*)nullptr,
-                         (const float4*)nullptr, (const uint16_t*)nullptr, (const int32_t*)nullptr,
-                         (const uchar4*)nullptr, desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, NoObs{});
-  } else {
-    OFX_CHECK_ARG(k >= 1 && k <= 4 && n_nodes >= k, "bad k/n_nodes");
-    OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
-    if (n_list == 0) return OFX_OK;
-    OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights, "null warp buffer");
+  int st = check_frame(a.desc, a.cam, a.cam && a.depth && a.tsdf && a.weight, "null buffer", a.color_im, a.color, &g);
+  if (st || (st = check_semantics(a.desc)) || (st = check_obs(a.desc, a.ow, &w))) return st;
+  const CamD c = make_cam(a.cam);
+  if (warp) {
+    OFX_CHECK_ARG(a.k >= 1 && a.k <= 4 && a.n_nodes >= a.k, "bad k/n_nodes");
+    OFX_CHECK_ARG(a.n_list >= 0 && a.n_list <= g.n_bricks, "bad n_list");
+    if (a.n_list == 0) return OFX_OK;
+    OFX_CHECK_ARG(a.packed_nodes && a.brick_list && a.anchors && a.weights, "null warp buffer");
     IntTimer timer;
-    if (ow)
-      OFX_TIMED_LAUNCH(timer, (k_integrate<true, false, false, true>), dim3((unsigned)n_list), dim3(256), 0, hs, g, c, depth,
-                       color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
-                       (const float4*)weights, (const uint16_t*)nullptr, (const int32_t*)nullptr,
-                       (const uchar4*)nullptr, desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, w);
+    launch_generic<true, false>(a, g, c, w, (unsigned)a.n_list, timer.e0, timer.e1);
+  } else {
+    // the generic source-frame form: pycuda semantics, shards of >= 2^31 voxels, or the OFX_INT_GENERIC A/B; a brick
+    // list (hash shard) is walked as in the warped form
+    const bool fast = fast_path(a.desc, g);
+    if (!fast) OFX_CHECK_ARG(a.brick_list == nullptr || (a.n_list >= 0 && a.n_list <= g.n_bricks), "bad n_list");
+    const unsigned nb = a.brick_list ? (unsigned)a.n_list : (unsigned)g.n_bricks;
+    if (nb == 0) return OFX_OK;
+    if (fast)
+      with_flags(a.color != nullptr, a.ow != nullptr, [&](auto COLOR, auto WT) {
+        launch(as_stream(a.s), nullptr, nullptr, k_integrate_src<COLOR(), WT()>, nb, g, make_div(g), c, a.depth,
+               a.color_im, a.brick_list, a.desc->trunc_margin, 1.0 / a.desc->trunc_margin, a.obs_weight, a.tsdf,
+               a.weight, a.color, a.n_updated, obs_of<WT()>(w));
+      });
     else
-      OFX_TIMED_LAUNCH(timer, pyc ? (k_integrate<true, false, true>) : (k_integrate<true, false, false>), dim3((unsigned)n_list),
-                       dim3(256), 0, hs, g, c, depth, color_im,
-                       (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors, (const float4*)weights,
-                       (const uint16_t*)nullptr, (const int32_t*)nullptr, (const uchar4*)nullptr,
-                       desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, NoObs{});
+      launch_generic<false, false>(a, g, c, w, nb, nullptr, nullptr);
   }
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
 
-int integrate_palette_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
-                           const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
-                           int32_t n_list, const uint16_t* anchors, const float* weights, const uint16_t* pal_ids,
-                           const int32_t* pal_n, const uint8_t* local_anchors, double obs_weight, float* tsdf,
-                           float* weight, float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
+// ofx_integrate_palette, ofx_integrate_palette_cull and their _w forms. With both scratch buffers, the per-frame brick
+// cull runs in front of k_integrate_pal4; it serves that kernel only (the cull itself reads the depth alone: a weight
+// only removes updates).
+int integrate_palette_impl(const IntCall& a) {
   BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  OFX_CHECK_ARG(cam && depth, "null camera/depth");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  OFX_CHECK_ARG(k >= 1 && k <= 4 && n_nodes >= k, "bad k/n_nodes");
-  OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
   ObsW w{};
-  if (ow) {
-    if ((st = check_obs(desc, ow))) return st;
-    w = ObsW{ow->obs_im, ow->w_max};
-  }
-  if (n_list == 0) return OFX_OK;
-  OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights && pal_ids && pal_n && local_anchors,
+  int st = check_frame(a.desc, a.cam, a.cam && a.depth, "null camera/depth", a.color_im, a.color, &g);
+  if (st) return st;
+  OFX_CHECK_ARG(a.k >= 1 && a.k <= 4 && a.n_nodes >= a.k, "bad k/n_nodes");
+  OFX_CHECK_ARG(a.n_list >= 0 && a.n_list <= g.n_bricks, "bad n_list");
+  if ((st = check_obs(a.desc, a.ow, &w))) return st;
+  if (a.n_list == 0) return OFX_OK;
+  OFX_CHECK_ARG(a.packed_nodes && a.brick_list && a.anchors && a.weights && a.pal_ids && a.pal_n && a.local_anchors,
                 "null warp/palette buffer");
-  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
-  IntTimer timer;
-  if (desc->semantics == OFX_SEM_CPU && k == 4 && g.n_bricks * kBrickVox < (1ll << 31) && !getenv("OFX_INT_GENERIC")) {
-    if (ow) {
-      if (color)
-        OFX_TIMED_LAUNCH(timer, (k_integrate_pal4<true, true>), dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g,
-                         make_div(g), make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
-                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
-                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                         (const uint8_t*)nullptr, w);
-      else
-        OFX_TIMED_LAUNCH(timer, (k_integrate_pal4<false, true>), dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g,
-                         make_div(g), make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
-                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
-                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                         (const uint8_t*)nullptr, w);
-    } else if (color)
-      OFX_TIMED_LAUNCH(timer, k_integrate_pal4<true>, dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_div(g),
-                         make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
-                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
-                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                         (const uint8_t*)nullptr, NoObs{});
-    else
-      OFX_TIMED_LAUNCH(timer, k_integrate_pal4<false>, dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_div(g),
-                         make_cam(cam), depth, color_im, (const float4*)packed_nodes, n_nodes, brick_list,
-                         (const ushort4*)anchors, (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors,
-                         desc->trunc_margin, 1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                         (const uint8_t*)nullptr, NoObs{});
-    OFX_LAUNCH_CHECK();
-    return OFX_OK;
+  if ((st = check_semantics(a.desc))) return st;
+  const hipStream_t hs = as_stream(a.s);
+  const CamD c = make_cam(a.cam);
+  IntTimer timer;   // with the cull: one event pair around the three kernels (tile max, cull, integrate)
+  if (a.k == 4 && fast_path(a.desc, g)) {
+    const BrickDiv bd = make_div(g);
+    const bool cull = a.tile_scratch && a.active;
+    if (cull) {
+      const int TW = (a.cam->width + 7) / 8, TH = (a.cam->height + 7) / 8;
+      launch(hs, timer.e0, nullptr, k_tile_max, grid_for((int64_t)TW * TH, 256), a.depth, a.cam->width, a.cam->height,
+             TW, TH, a.tile_scratch);
+      launch(hs, nullptr, nullptr, k_brick_cull, (unsigned)((a.n_list + 15) / 16), g, bd, c,
+             (const float4*)a.packed_nodes, a.n_nodes, a.brick_list, a.pal_ids, a.pal_n, a.n_list, a.tile_scratch, TW,
+             TH, a.desc->trunc_margin, a.active);
+    }
+    with_flags(a.color != nullptr, a.ow != nullptr, [&](auto COLOR, auto WT) {
+      launch(hs, cull ? nullptr : timer.e0, timer.e1, k_integrate_pal4<COLOR(), WT()>, (unsigned)a.n_list, g, bd, c,
+             a.depth, a.color_im, (const float4*)a.packed_nodes, a.n_nodes, a.brick_list, (const ushort4*)a.anchors,
+             (const float4*)a.weights, a.pal_ids, a.pal_n, (const uchar4*)a.local_anchors, a.desc->trunc_margin,
+             1.0 / a.desc->trunc_margin, a.obs_weight, a.tsdf, a.weight, a.color, a.n_updated,
+             cull ? a.active : nullptr, obs_of<WT()>(w));
+    });
+  } else {
+    launch_generic<true, true>(a, g, c, w, (unsigned)a.n_list, timer.e0, timer.e1);
   }
-  if (ow)
-    OFX_TIMED_LAUNCH(timer, (k_integrate<true, true, false, true>), dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g,
-                     make_cam(cam), depth, color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
-                     (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin, obs_weight,
-                     tsdf, weight, color, n_updated, w);
-  else
-    OFX_TIMED_LAUNCH(timer, desc->semantics == OFX_SEM_PYCUDA ? (k_integrate<true, true, true>) : (k_integrate<true, true, false>),
-                     dim3((unsigned)n_list), dim3(256), 0, as_stream(s), g, make_cam(cam),
-                     depth, color_im, (const float4*)packed_nodes, k, brick_list, (const ushort4*)anchors,
-                     (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
-                     obs_weight, tsdf, weight, color, n_updated, NoObs{});
+  OFX_LAUNCH_CHECK();
+  return OFX_OK;
+}
+
+// ofx_integrate_points and ofx_integrate_points_w
+int integrate_points_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
+                          const float* points, const int64_t* voxel_ids, const uint8_t* valid, int64_t n_points,
+                          double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
+                          const ofx_obs_weights* ow, ofx_stream_t s) {
+  BrickGeom g;
+  ObsW w{};
+  int st = check_frame(desc, cam, cam && depth && tsdf && weight && n_points >= 0, "null buffer / bad size", color_im,
+                       color, &g);
+  if (st || (st = check_obs(desc, ow, &w)) || (st = check_semantics(desc))) return st;
+  if (n_points == 0) return OFX_OK;
+  OFX_CHECK_ARG(points && voxel_ids, "null points / voxel ids");
+  with_flags(desc->semantics == OFX_SEM_PYCUDA, ow != nullptr, [&](auto PYC, auto WT) {
+    if constexpr (!(PYC() && WT()))   // (as in launch_generic)
+      launch(as_stream(s), nullptr, nullptr, k_integrate_points<PYC(), WT()>, grid_for(n_points, 256, 1 << 30), g,
+             make_cam(cam), depth, color_im, points, voxel_ids, valid, n_points, desc->trunc_margin,
+             1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, obs_of<WT()>(w));
+  });
   OFX_LAUNCH_CHECK();
   return OFX_OK;
 }
@@ -1118,8 +1152,9 @@ int ofx_integrate(const ofx_volume_desc* desc, const ofx_camera* cam, const floa
                   int32_t warp, const float* packed_nodes, int32_t n_nodes, int32_t k, const int32_t* brick_list,
                   int32_t n_list, const uint16_t* anchors, const float* weights, double obs_weight, float* tsdf,
                   float* weight, float* color, uint32_t* n_updated, ofx_stream_t s) {
-  return integrate_impl(desc, cam, depth, color_im, warp, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
-                        obs_weight, tsdf, weight, color, n_updated, nullptr, s);
+  return integrate_impl({desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                         nullptr, nullptr, nullptr, obs_weight, tsdf, weight, color, n_updated, nullptr, nullptr, nullptr,
+                         s}, warp);
 }
 
 int ofx_integrate_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,
@@ -1127,8 +1162,9 @@ int ofx_integrate_w(const ofx_volume_desc* desc, const ofx_camera* cam, const fl
                     int32_t n_list, const uint16_t* anchors, const float* weights, double obs_weight, float* tsdf,
                     float* weight, float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
   OFX_CHECK_ARG(ow, "null observation weights");
-  return integrate_impl(desc, cam, depth, color_im, warp, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
-                        obs_weight, tsdf, weight, color, n_updated, ow, s);
+  return integrate_impl({desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
+                         nullptr, nullptr, nullptr, obs_weight, tsdf, weight, color, n_updated, nullptr, nullptr, ow, s},
+                        warp);
 }
 
 int ofx_integrate_palette(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
@@ -1137,8 +1173,9 @@ int ofx_integrate_palette(const ofx_volume_desc* desc, const ofx_camera* cam, co
                           const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
                           double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                           ofx_stream_t s) {
-  return integrate_palette_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
-                                pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, nullptr, s);
+  return integrate_palette_impl({desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
+                                 weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated,
+                                 nullptr, nullptr, nullptr, s});
 }
 
 int ofx_integrate_palette_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
@@ -1148,73 +1185,9 @@ int ofx_integrate_palette_w(const ofx_volume_desc* desc, const ofx_camera* cam, 
                             double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                             const ofx_obs_weights* ow, ofx_stream_t s) {
   OFX_CHECK_ARG(ow, "null observation weights");
-  return integrate_palette_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
-                                pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, ow, s);
-}
-
-static int integrate_cull_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
-                               const float* color_im, const float* packed_nodes, int32_t n_nodes, int32_t k,
-                               const int32_t* brick_list, int32_t n_list, const uint16_t* anchors, const float* weights,
-                               const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
-                               double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
-                               float* tile_scratch, uint8_t* active, const ofx_obs_weights* ow, ofx_stream_t s) {
-  BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  OFX_CHECK_ARG(cam && depth, "null camera/depth");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  ObsW w{};
-  if (ow) {
-    if ((st = check_obs(desc, ow))) return st;
-    w = ObsW{ow->obs_im, ow->w_max};
-  }
-  const bool fast = desc->semantics == OFX_SEM_CPU && k == 4 && g.n_bricks * kBrickVox < (1ll << 31) &&
-                    !getenv("OFX_INT_GENERIC");
-  if (!fast || !tile_scratch || !active)   // the cull serves the CPU-semantics K = 4 palette kernel only
-    return integrate_palette_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
-                                  weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, ow, s);
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  OFX_CHECK_ARG(n_nodes >= k, "bad k/n_nodes");
-  OFX_CHECK_ARG(n_list >= 0 && n_list <= g.n_bricks, "bad n_list");
-  if (n_list == 0) return OFX_OK;
-  OFX_CHECK_ARG(packed_nodes && brick_list && anchors && weights && pal_ids && pal_n && local_anchors,
-                "null warp/palette buffer");
-  hipStream_t hs = as_stream(s);
-  const CamD c = make_cam(cam);
-  const BrickDiv bd = make_div(g);
-  const int TW = (cam->width + 7) / 8, TH = (cam->height + 7) / 8;
-  IntTimer timer;   // one event pair around the three kernels (tile max, cull, integrate)
-  if (timer.e0)
-    hipExtLaunchKernelGGL(k_tile_max, dim3(grid_for((int64_t)TW * TH, 256)), dim3(256), 0, hs, timer.e0, nullptr, 0,
-                          depth, cam->width, cam->height, TW, TH, tile_scratch);
-  else
-    hipLaunchKernelGGL(k_tile_max, dim3(grid_for((int64_t)TW * TH, 256)), dim3(256), 0, hs, depth, cam->width,
-                       cam->height, TW, TH, tile_scratch);
-  hipLaunchKernelGGL(k_brick_cull, dim3((unsigned)((n_list + 15) / 16)), dim3(256), 0, hs, g, bd, c,
-                     (const float4*)packed_nodes, n_nodes, brick_list, pal_ids, pal_n, n_list,
-                     (const float*)tile_scratch, TW, TH, desc->trunc_margin, active);
-  // (extra: the kernel's last argument, NoObs or the weighted form's ObsW — the cull itself reads the depth alone: a weight only removes updates)
-  auto launch = [&](auto kern, auto... extra) {
-    if (timer.e0)
-      hipExtLaunchKernelGGL(kern, dim3((unsigned)n_list), dim3(256), 0, hs, nullptr, timer.e1, 0, g, bd, c, depth,
-                            color_im, (const float4*)packed_nodes, n_nodes, brick_list, (const ushort4*)anchors,
-                            (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
-                            1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated,
-                            (const uint8_t*)active, extra...);
-    else
-      hipLaunchKernelGGL(kern, dim3((unsigned)n_list), dim3(256), 0, hs, g, bd, c, depth, color_im,
-                         (const float4*)packed_nodes, n_nodes, brick_list, (const ushort4*)anchors,
-                         (const float4*)weights, pal_ids, pal_n, (const uchar4*)local_anchors, desc->trunc_margin,
-                         1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, (const uint8_t*)active,
-                         extra...);
-  };
-  if (ow) {
-    if (color) launch((k_integrate_pal4<true, true>), w);
-    else launch((k_integrate_pal4<false, true>), w);
-  } else if (color) launch(k_integrate_pal4<true>, NoObs{});
-  else launch(k_integrate_pal4<false>, NoObs{});
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  return integrate_palette_impl({desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
+                                 weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated,
+                                 nullptr, nullptr, ow, s});
 }
 
 int ofx_integrate_palette_cull(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
@@ -1223,9 +1196,9 @@ int ofx_integrate_palette_cull(const ofx_volume_desc* desc, const ofx_camera* ca
                                const uint16_t* pal_ids, const int32_t* pal_n, const uint8_t* local_anchors,
                                double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                                float* tile_scratch, uint8_t* active, ofx_stream_t s) {
-  return integrate_cull_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
-                             pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, tile_scratch,
-                             active, nullptr, s);
+  return integrate_palette_impl({desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
+                                 weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated,
+                                 tile_scratch, active, nullptr, s});
 }
 
 int ofx_integrate_palette_cull_w(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
@@ -1235,36 +1208,9 @@ int ofx_integrate_palette_cull_w(const ofx_volume_desc* desc, const ofx_camera* 
                                  double obs_weight, float* tsdf, float* weight, float* color, uint32_t* n_updated,
                                  float* tile_scratch, uint8_t* active, const ofx_obs_weights* ow, ofx_stream_t s) {
   OFX_CHECK_ARG(ow, "null observation weights");
-  return integrate_cull_impl(desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights,
-                             pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated, tile_scratch,
-                             active, ow, s);
-}
-
-static int integrate_points_impl(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth,
-                                 const float* color_im, const float* points, const int64_t* voxel_ids,
-                                 const uint8_t* valid, int64_t n_points, double obs_weight, float* tsdf, float* weight,
-                                 float* color, uint32_t* n_updated, const ofx_obs_weights* ow, ofx_stream_t s) {
-  BrickGeom g;
-  int st = make_geom(desc, &g);
-  if (st) return st;
-  if (ow && (st = check_obs(desc, ow))) return st;
-  OFX_CHECK_ARG(cam && depth && tsdf && weight && n_points >= 0, "null buffer / bad size");
-  OFX_CHECK_ARG(cam->width > 0 && cam->height > 0, "bad camera size");
-  OFX_CHECK_ARG((color == nullptr) == (color_im == nullptr), "color and color_im must both be set or both NULL");
-  OFX_CHECK_ARG(desc->semantics == OFX_SEM_CPU || desc->semantics == OFX_SEM_PYCUDA, "bad semantics %d", desc->semantics);
-  if (n_points == 0) return OFX_OK;
-  OFX_CHECK_ARG(points && voxel_ids, "null points / voxel ids");
-  if (ow)
-    hipLaunchKernelGGL((k_integrate_points<false, true>), dim3(grid_for(n_points, 256, 1 << 30)), dim3(256), 0, as_stream(s), g,
-                       make_cam(cam), depth, color_im, points, voxel_ids, valid, n_points, desc->trunc_margin,
-                       1.0 / desc->trunc_margin, obs_weight, tsdf, weight, color, n_updated, ObsW{ow->obs_im, ow->w_max});
-  else
-    hipLaunchKernelGGL(desc->semantics == OFX_SEM_PYCUDA ? (k_integrate_points<true>) : (k_integrate_points<false>),
-                     dim3(grid_for(n_points, 256, 1 << 30)), dim3(256), 0, as_stream(s), g, make_cam(cam), depth,
-                     color_im, points, voxel_ids, valid, n_points, desc->trunc_margin, 1.0 / desc->trunc_margin,
-                     obs_weight, tsdf, weight, color, n_updated, NoObs{});
-  OFX_LAUNCH_CHECK();
-  return OFX_OK;
+  return integrate_palette_impl({desc, cam, depth, color_im, packed_nodes, n_nodes, k, brick_list, n_list, anchors,
+                                 weights, pal_ids, pal_n, local_anchors, obs_weight, tsdf, weight, color, n_updated,
+                                 tile_scratch, active, ow, s});
 }
 
 int ofx_integrate_points(const ofx_volume_desc* desc, const ofx_camera* cam, const float* depth, const float* color_im,

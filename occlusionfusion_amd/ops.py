@@ -76,6 +76,51 @@ def _stream(t):
 
 
 # --------------------------------------------------------------------------------------------- integrate
+def _obs_weights(obs_im, depth, w_max):
+    if obs_im.dtype != torch.float32 or tuple(obs_im.shape) != tuple(depth.shape):
+        raise ValueError(f"weighted integrate: obs_im must be float32 of the depth's shape {tuple(depth.shape)}, got "
+                         f"{obs_im.dtype} {tuple(obs_im.shape)}")
+    if not obs_im.is_contiguous():
+        raise ValueError("weighted integrate: obs_im must be contiguous")
+    return _lib.ObsWeights(obs_im.data_ptr(), float(w_max), 0.0)
+
+
+def _integrate_call(ow, name, frame, *args):
+    """The one library call of an integrate operator: entry point `name` with the arguments `frame` that all four
+    operators begin with (tsdf ... obs_weight) and its own `args`; with observation weights ow (_obs_weights; None:
+    unweighted) its _w form, which takes ow in front of the stream."""
+    (tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics, intr,
+     obs_weight) = frame
+    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
+    cam = _camera(intr, depth.shape[0], depth.shape[1])
+    call(name if ow is None else name + "_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), *args,
+         float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), *(() if ow is None else (byref(ow),)),
+         _stream(tsdf))
+
+
+def _integrate(ow, *a):
+    """integrate (ow None) / integrate_weighted: a = integrate's arguments."""
+    frame, (packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights, pal_ids, pal_n, local) = a[:14], a[14:]
+    if packed_nodes is None:   # source frame; brick_list: a hash shard's own bricks (None: all of the shard)
+        _integrate_call(ow, "ofx_integrate", frame, 0, None, 0, 1, ptr(brick_list), n_list, None, None)
+    elif pal_ids is not None:
+        _integrate_call(ow, "ofx_integrate_palette", frame, ptr(packed_nodes), n_nodes, k, ptr(brick_list), n_list,
+                        ptr(anchors), ptr(weights), ptr(pal_ids), ptr(pal_n), ptr(local))
+    else:
+        _integrate_call(ow, "ofx_integrate", frame, 1, ptr(packed_nodes), n_nodes, k, ptr(brick_list), n_list,
+                        ptr(anchors), ptr(weights))
+
+
+def _integrate_points(ow, *a):
+    """integrate_points (ow None) / integrate_points_weighted: a = integrate_points' arguments."""
+    frame, (points, voxel_ids, valid) = a[:14], a[14:]
+    _integrate_call(ow, "ofx_integrate_points", frame, ptr(points), ptr(voxel_ids), ptr(valid), points.shape[0])
+
+
+def _no_result(*args):
+    """The fake kernel of the four integrate operators: they mutate their first arguments and return nothing."""
+    return None
+
 @_op("integrate", mutates_args=("tsdf", "weight", "color", "n_updated"))
 def integrate(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], n_updated: Optional[Tensor], depth: Tensor,
               color_im: Optional[Tensor], dims: List[int], brick_range: List[int], origin: List[float],
@@ -86,26 +131,12 @@ def integrate(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], n_updated: 
     """TSDFVolume.integrate's device work (tsdf.py:378-494): source frame when packed_nodes is None
     (ofx_integrate warp=0), else the fused skin-cache ED warp + integrate of the listed bricks — through the
     LDS node palette when pal_ids is given (ofx_integrate_palette), with global node gathers otherwise."""
-    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
-    cam = _camera(intr, depth.shape[0], depth.shape[1])
-    s = _stream(tsdf)
-    if packed_nodes is None:   # source frame; brick_list: a hash shard's own bricks (None: all of the shard)
-        call("ofx_integrate", byref(desc), byref(cam), ptr(depth), ptr(color_im), 0, None, 0, 1, ptr(brick_list),
-             n_list, None, None, float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), s)
-    elif pal_ids is not None:
-        call("ofx_integrate_palette", byref(desc), byref(cam), ptr(depth), ptr(color_im), ptr(packed_nodes), n_nodes, k,
-             ptr(brick_list), n_list, ptr(anchors), ptr(weights), ptr(pal_ids), ptr(pal_n), ptr(local),
-             float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), s)
-    else:
-        call("ofx_integrate", byref(desc), byref(cam), ptr(depth), ptr(color_im), 1, ptr(packed_nodes), n_nodes, k,
-             ptr(brick_list), n_list, ptr(anchors), ptr(weights), float(obs_weight), ptr(tsdf), ptr(weight),
-             ptr(color), ptr(n_updated), s)
+    _integrate(None, tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin,
+               semantics, intr, obs_weight, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights, pal_ids, pal_n,
+               local)
 
 
-@integrate.register_fake
-def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics,
-      intr, obs_weight, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights, pal_ids, pal_n, local):
-    return None
+integrate.register_fake(_no_result)
 
 
 @_op("integrate_points", mutates_args=("tsdf", "weight", "color", "n_updated"))
@@ -115,27 +146,11 @@ def integrate_points(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], n_up
                      obs_weight: float, points: Tensor, voxel_ids: Tensor, valid: Optional[Tensor]) -> None:
     """TSDFVolume.integrate of given (already deformed) points into the voxels `voxel_ids` (C-order ids,
     distinct): tsdf.py:442-494 with pts from WarpField.deform_tsdf (warpfield.py:369-380)."""
-    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
-    cam = _camera(intr, depth.shape[0], depth.shape[1])
-    call("ofx_integrate_points", byref(desc), byref(cam), ptr(depth), ptr(color_im), ptr(points), ptr(voxel_ids),
-         ptr(valid), points.shape[0], float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated),
-         _stream(tsdf))
+    _integrate_points(None, tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size,
+                      trunc_margin, semantics, intr, obs_weight, points, voxel_ids, valid)
 
 
-@integrate_points.register_fake
-def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics,
-      intr, obs_weight, points, voxel_ids, valid):
-    return None
-
-
-# --------------------------------------------------------------------------------------------- weighted integrate
-def _obs_weights(obs_im, depth, w_max):
-    if obs_im.dtype != torch.float32 or tuple(obs_im.shape) != tuple(depth.shape):
-        raise ValueError(f"weighted integrate: obs_im must be float32 of the depth's shape {tuple(depth.shape)}, got "
-                         f"{obs_im.dtype} {tuple(obs_im.shape)}")
-    if not obs_im.is_contiguous():
-        raise ValueError("weighted integrate: obs_im must be contiguous")
-    return _lib.ObsWeights(obs_im.data_ptr(), float(w_max), 0.0)
+integrate_points.register_fake(_no_result)
 
 
 @_op("integrate_weighted", mutates_args=("tsdf", "weight", "color", "n_updated"))
@@ -148,28 +163,12 @@ def integrate_weighted(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], n_
     """torch.ops.ofx.integrate with a per-pixel observation-weight image obs_im (f32, the depth's shape) and a cap w_max
     on the stored weight (inf: none): ofx_integrate_w / ofx_integrate_palette_w (new capability, CPU semantics only; off
     by default — nothing calls it unless a weight image or a cap is asked for)."""
-    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
-    cam = _camera(intr, depth.shape[0], depth.shape[1])
-    ow = _obs_weights(obs_im, depth, w_max)
-    s = _stream(tsdf)
-    if packed_nodes is None:
-        call("ofx_integrate_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), 0, None, 0, 1, ptr(brick_list),
-             n_list, None, None, float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), byref(ow), s)
-    elif pal_ids is not None:
-        call("ofx_integrate_palette_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), ptr(packed_nodes), n_nodes, k,
-             ptr(brick_list), n_list, ptr(anchors), ptr(weights), ptr(pal_ids), ptr(pal_n), ptr(local),
-             float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), byref(ow), s)
-    else:
-        call("ofx_integrate_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), 1, ptr(packed_nodes), n_nodes, k,
-             ptr(brick_list), n_list, ptr(anchors), ptr(weights), float(obs_weight), ptr(tsdf), ptr(weight),
-             ptr(color), ptr(n_updated), byref(ow), s)
+    _integrate(_obs_weights(obs_im, depth, w_max), tsdf, weight, color, n_updated, depth, color_im, dims, brick_range,
+               origin, voxel_size, trunc_margin, semantics, intr, obs_weight, packed_nodes, n_nodes, k, brick_list, n_list,
+               anchors, weights, pal_ids, pal_n, local)
 
 
-@integrate_weighted.register_fake
-def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics,
-      intr, obs_weight, packed_nodes, n_nodes, k, brick_list, n_list, anchors, weights, pal_ids, pal_n, local, obs_im,
-      w_max):
-    return None
+integrate_weighted.register_fake(_no_result)
 
 
 @_op("integrate_points_weighted", mutates_args=("tsdf", "weight", "color", "n_updated"))
@@ -179,18 +178,11 @@ def integrate_points_weighted(tsdf: Tensor, weight: Tensor, color: Optional[Tens
                               intr: List[float], obs_weight: float, points: Tensor, voxel_ids: Tensor,
                               valid: Optional[Tensor], obs_im: Tensor, w_max: float) -> None:
     """torch.ops.ofx.integrate_points with an observation-weight image and a weight cap (ofx_integrate_points_w)."""
-    desc = _volume_desc(dims, brick_range, origin, voxel_size, trunc_margin, semantics)
-    cam = _camera(intr, depth.shape[0], depth.shape[1])
-    ow = _obs_weights(obs_im, depth, w_max)
-    call("ofx_integrate_points_w", byref(desc), byref(cam), ptr(depth), ptr(color_im), ptr(points), ptr(voxel_ids),
-         ptr(valid), points.shape[0], float(obs_weight), ptr(tsdf), ptr(weight), ptr(color), ptr(n_updated), byref(ow),
-         _stream(tsdf))
+    _integrate_points(_obs_weights(obs_im, depth, w_max), tsdf, weight, color, n_updated, depth, color_im, dims,
+                      brick_range, origin, voxel_size, trunc_margin, semantics, intr, obs_weight, points, voxel_ids, valid)
 
 
-@integrate_points_weighted.register_fake
-def _(tsdf, weight, color, n_updated, depth, color_im, dims, brick_range, origin, voxel_size, trunc_margin, semantics,
-      intr, obs_weight, points, voxel_ids, valid, obs_im, w_max):
-    return None
+integrate_points_weighted.register_fake(_no_result)
 
 
 @_op("observation_weights", mutates_args=())

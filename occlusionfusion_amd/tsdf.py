@@ -330,6 +330,22 @@ class TSDFVolume:
             raise ValueError(f"weight_image must have the depth image's shape {(H, W)}, got {tuple(w.shape)}")
         return w
 
+    def _op_geometry(self, obs_weight):
+        """The integrate operators' arguments dims ... obs_weight: the shard, the camera and the frame's weight."""
+        d, K = self.desc, self.cam_intr
+        return ([int(v) for v in d.dim], [self.brick_x0, self.brick_x1], [float(v) for v in d.origin],
+                float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
+                [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])], float(obs_weight))
+
+    def _cull_scratch(self, n_list):
+        """The brick cull's (tile maxima, per-slot flags), regrown when the frame or the brick list outgrows them."""
+        H, W = (int(v) for v in self.depth_t.shape)
+        nt = ((W + 7) // 8) * ((H + 7) // 8)
+        if self._cull is None or self._cull[0].numel() < nt or self._cull[1].numel() < n_list:
+            self._cull = (torch.empty(nt, dtype=torch.float32, device=self.device),
+                          torch.empty(max(1, n_list), dtype=torch.uint8, device=self.device))
+        return self._cull
+
     def integrate_device(self, obs_weight=1., count_updates=False, weight_image=None, max_weight=None):
         """Integrate the current (already updated) frame through torch.ops.ofx.integrate (the warped palette path:
         its library call directly); no host sync.
@@ -338,95 +354,41 @@ class TSDFVolume:
         reference has none). A voxel's observation counts obs_weight · weight_image[its pixel] — a pixel whose weight
         is not a finite number > 0 updates nothing — and the stored weight is capped at max_weight, so the model keeps
         adapting. With both None, and no fusion_weights set on the volume, the calls are the unweighted ones, argument
-        for argument; with fusion_weights set, the map built when the frame was staged / updated is used."""
+        for argument; with fusion_weights set, the map built when the frame was staged / updated is used. Every path
+        takes the weighted form of its operator or library entry (the same kernels' weighted forms) when a weight
+        image is in force."""
         on, w_max = self._check_weighted(weight_image, max_weight)
         if not on and self.obs_t is not None:
             if self.semantics != "cpu":
                 raise ValueError("fusion_weights needs 'cpu' integrate semantics")
             on, weight_image, w_max = True, self.obs_t, self.obs_wmax
-        if on:
-            return self._integrate_weighted(obs_weight, count_updates, self._weight_image(weight_image), w_max)
-        src = _opt(self.fopt, "source_frame", 0)
+        wi = self._weight_image(weight_image) if on else None
         color = self.color_b if self.with_color else None
         color_im = self.color_t if self.with_color else None
         nu = self.n_updated if count_updates else None
-        d = self.desc
-        geo = lambda: ([int(v) for v in d.dim], [self.brick_x0, self.brick_x1], [float(v) for v in d.origin],
-                       float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
-                       [float(self.cam_intr[0, 0]), float(self.cam_intr[1, 1]), float(self.cam_intr[0, 2]),
-                        float(self.cam_intr[1, 2])], float(obs_weight))
-        if self.frame_id == src:
-            ob = self.owned_bricks
-            torch.ops.ofx.integrate(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *geo(),
-                                    None, 0, 1, ob, 0 if ob is None else int(ob.shape[0]), None, None, None, None, None)
-            return
-        if self.warpfield is None:
-            raise RuntimeError("non-source frame integrate needs tsdf.warpfield (WarpField) to be set")
-        cache = self.warpfield.skin_tsdf_cache()
-        nodes = self.warpfield.packed_nodes()
-        pal = self.use_palette and cache.pal_n is not None
-        if pal:   # the frame loop's path: the library call of torch.ops.ofx.integrate's palette branch, made directly
-            args = (byref(d), byref(self.camera()), ptr(self.depth_t), ptr(color_im), ptr(nodes),
-                    self.warpfield.num_nodes, cache.k, ptr(cache.brick_list), cache.n_list, ptr(cache.anchors),
-                    ptr(cache.weights), ptr(cache.pal_ids), ptr(cache.pal_n), ptr(cache.local), float(obs_weight),
-                    ptr(self.tsdf_b), ptr(self.weight_b), ptr(color), ptr(nu))
-            if self.brick_cull:
-                H, W = (int(v) for v in self.depth_t.shape)
-                nt = ((W + 7) // 8) * ((H + 7) // 8)
-                if self._cull is None or self._cull[0].numel() < nt or self._cull[1].numel() < cache.n_list:
-                    self._cull = (torch.empty(nt, dtype=torch.float32, device=self.device),
-                                  torch.empty(max(1, cache.n_list), dtype=torch.uint8, device=self.device))
-                call("ofx_integrate_palette_cull", *args, ptr(self._cull[0]), ptr(self._cull[1]), stream_ptr())
-            else:
-                call("ofx_integrate_palette", *args, stream_ptr())
-            return
-        torch.ops.ofx.integrate(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *geo(),
-                                nodes, self.warpfield.num_nodes, cache.k, cache.brick_list, cache.n_list,
-                                cache.anchors, cache.weights, cache.pal_ids if pal else None,
-                                cache.pal_n if pal else None, cache.local if pal else None)
 
-    def _integrate_weighted(self, obs_weight, count_updates, wi, w_max):
-        """integrate_device's paths, one for one, through the _w entry points (the same kernels' weighted forms)."""
-        src = _opt(self.fopt, "source_frame", 0)
-        color = self.color_b if self.with_color else None
-        color_im = self.color_t if self.with_color else None
-        nu = self.n_updated if count_updates else None
-        d = self.desc
-        geo = ([int(v) for v in d.dim], [self.brick_x0, self.brick_x1], [float(v) for v in d.origin],
-               float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
-               [float(self.cam_intr[0, 0]), float(self.cam_intr[1, 1]), float(self.cam_intr[0, 2]),
-                float(self.cam_intr[1, 2])], float(obs_weight))
-        if self.frame_id == src:
+        def op(*warp):   # the paths off the frame loop: torch.ops.ofx.integrate(_weighted) with packed_nodes ... local
+            f, tail = (torch.ops.ofx.integrate_weighted, (wi, w_max)) if on else (torch.ops.ofx.integrate, ())
+            f(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *self._op_geometry(obs_weight), *warp, *tail)
+
+        if self.frame_id == _opt(self.fopt, "source_frame", 0):
             ob = self.owned_bricks
-            torch.ops.ofx.integrate_weighted(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *geo,
-                                             None, 0, 1, ob, 0 if ob is None else int(ob.shape[0]), None, None, None,
-                                             None, None, wi, w_max)
-            return
+            return op(None, 0, 1, ob, 0 if ob is None else int(ob.shape[0]), None, None, None, None, None)
         if self.warpfield is None:
             raise RuntimeError("non-source frame integrate needs tsdf.warpfield (WarpField) to be set")
         cache = self.warpfield.skin_tsdf_cache()
         nodes = self.warpfield.packed_nodes()
-        pal = self.use_palette and cache.pal_n is not None
-        if pal:
-            ow = _lib.ObsWeights(wi.data_ptr(), w_max, 0.0)
-            args = (byref(d), byref(self.camera()), ptr(self.depth_t), ptr(color_im), ptr(nodes),
-                    self.warpfield.num_nodes, cache.k, ptr(cache.brick_list), cache.n_list, ptr(cache.anchors),
-                    ptr(cache.weights), ptr(cache.pal_ids), ptr(cache.pal_n), ptr(cache.local), float(obs_weight),
-                    ptr(self.tsdf_b), ptr(self.weight_b), ptr(color), ptr(nu))
-            if self.brick_cull:
-                H, W = (int(v) for v in self.depth_t.shape)
-                nt = ((W + 7) // 8) * ((H + 7) // 8)
-                if self._cull is None or self._cull[0].numel() < nt or self._cull[1].numel() < cache.n_list:
-                    self._cull = (torch.empty(nt, dtype=torch.float32, device=self.device),
-                                  torch.empty(max(1, cache.n_list), dtype=torch.uint8, device=self.device))
-                call("ofx_integrate_palette_cull_w", *args, ptr(self._cull[0]), ptr(self._cull[1]), byref(ow),
-                     stream_ptr())
-            else:
-                call("ofx_integrate_palette_w", *args, byref(ow), stream_ptr())
-            return
-        torch.ops.ofx.integrate_weighted(self.tsdf_b, self.weight_b, color, nu, self.depth_t, color_im, *geo,
-                                         nodes, self.warpfield.num_nodes, cache.k, cache.brick_list, cache.n_list,
-                                         cache.anchors, cache.weights, None, None, None, wi, w_max)
+        if not (self.use_palette and cache.pal_n is not None):   # global anchors
+            return op(nodes, self.warpfield.num_nodes, cache.k, cache.brick_list, cache.n_list, cache.anchors,
+                      cache.weights, None, None, None)
+        # the frame loop's path: the library call of the operator's palette branch, made directly
+        ow = _lib.ObsWeights(wi.data_ptr(), w_max, 0.0) if on else None
+        scratch = self._cull_scratch(cache.n_list) if self.brick_cull else ()
+        call("ofx_integrate_palette" + ("_cull" if self.brick_cull else "") + ("_w" if on else ""), byref(self.desc),
+             byref(self.camera()), ptr(self.depth_t), ptr(color_im), ptr(nodes), self.warpfield.num_nodes, cache.k,
+             ptr(cache.brick_list), cache.n_list, ptr(cache.anchors), ptr(cache.weights), ptr(cache.pal_ids),
+             ptr(cache.pal_n), ptr(cache.local), float(obs_weight), ptr(self.tsdf_b), ptr(self.weight_b), ptr(color),
+             ptr(nu), *(ptr(t) for t in scratch), *((byref(ow),) if on else ()), stream_ptr())
 
     def integrate_points(self, points, voxel_ids, valid=None, obs_weight=1., count_updates=False, weight_image=None,
                          max_weight=None):
@@ -436,27 +398,16 @@ class TSDFVolume:
         weight_image / max_weight: the weighted integrate, as integrate_device takes them (a fusion_weights map of
         the volume is not applied here: explicit points come with explicit weights)."""
         on, w_max = self._check_weighted(weight_image, max_weight)
-        d = self.desc
         pts = torch.as_tensor(points, dtype=torch.float32, device=self.device).reshape(-1, 3).contiguous()
         vox = torch.as_tensor(voxel_ids, dtype=torch.int64, device=self.device).reshape(-1).contiguous()
         if vox.shape[0] != pts.shape[0]:
             raise ValueError(f"{pts.shape[0]} points but {vox.shape[0]} voxel ids")
         v = None if valid is None else torch.as_tensor(valid, device=self.device).reshape(-1).to(torch.uint8)
         cnt = torch.zeros(1, dtype=torch.int32, device=self.device) if count_updates else None
-        if on:
-            torch.ops.ofx.integrate_points_weighted(
-                self.tsdf_b, self.weight_b, self.color_b if self.with_color else None, cnt, self.depth_t,
-                self.color_t if self.with_color else None, [int(x) for x in d.dim], [self.brick_x0, self.brick_x1],
-                [float(x) for x in d.origin], float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
-                [float(self.cam_intr[0, 0]), float(self.cam_intr[1, 1]), float(self.cam_intr[0, 2]),
-                 float(self.cam_intr[1, 2])], float(obs_weight), pts, vox, v, self._weight_image(weight_image), w_max)
-            return cnt
-        torch.ops.ofx.integrate_points(
-            self.tsdf_b, self.weight_b, self.color_b if self.with_color else None, cnt, self.depth_t,
-            self.color_t if self.with_color else None, [int(x) for x in d.dim], [self.brick_x0, self.brick_x1],
-            [float(x) for x in d.origin], float(d.voxel_size), float(d.trunc_margin), int(d.semantics),
-            [float(self.cam_intr[0, 0]), float(self.cam_intr[1, 1]), float(self.cam_intr[0, 2]),
-             float(self.cam_intr[1, 2])], float(obs_weight), pts, vox, v)
+        f, tail = ((torch.ops.ofx.integrate_points_weighted, (self._weight_image(weight_image), w_max)) if on else
+                   (torch.ops.ofx.integrate_points, ()))
+        f(self.tsdf_b, self.weight_b, self.color_b if self.with_color else None, cnt, self.depth_t,
+          self.color_t if self.with_color else None, *self._op_geometry(obs_weight), pts, vox, v, *tail)
         return cnt
 
     def raycast(self, cam_intr=None, height=None, width=None, z_near=0.1, z_far=10.0):

@@ -165,6 +165,44 @@ def test_a_weighted_warped_integrate(A, config, monkeypatch):
         vol.brick_cull, vol.use_palette, vol.with_color = True, True, True
 
 
+def test_a_integrate_timing_hook(A, cuda, points_case, monkeypatch):
+    """TSDFVolume.integrate_timing (ofx_integrate_timing: what bench.py divides its kernel time by). Armed, every warped
+    integrate_device — with the cull (three kernels, one event pair), without it, with global anchors and through the
+    generic palette kernel, plain and with the weight image — records exactly one launch with a finite time > 0; the
+    source frame and integrate_points record none; disarmed, a warped integrate records none."""
+    from occlusionfusion_amd import TSDFVolume
+    vol, sc, timing = A.vol, A.sc, TSDFVolume.integrate_timing
+    assert (A.pn > sr.PAL).sum() >= 20
+    timing(True)                                         # arm, and drop whatever was recorded before
+    try:
+        for config in ("cull", "nocull", "global", "generic"):
+            with monkeypatch.context() as m:
+                if config == "generic":
+                    m.setenv("OFX_INT_GENERIC", "1")
+                vol.brick_cull, vol.use_palette = config == "cull", config != "global"
+                for kw in ({}, dict(weight_image=A.wim_t)):
+                    _fuse(vol, sc.state, sc.im, 1.0, **kw)
+                    ms, n = timing(True)
+                    print(f"integrate_timing {config} {'weighted' if kw else 'plain'}: {ms:.4f} ms, {n} launch(es)")
+                    assert n == 1 and 0 < ms < INF, (config, sorted(kw), ms, n)
+        d = sr.scene_d()
+        for kw in ({}, dict(weight_image=torch.ones((d.height, d.width), dtype=torch.float32, device=cuda))):
+            _fuse(_volume(d, cuda), d.state, d.im, 1.0, frame=0, **kw)
+            assert timing(True) == (0.0, 0)
+        c = points_case
+        for kw in ({}, dict(weight_image=torch.from_numpy(c.wim).to(cuda))):
+            _points_volume(c, cuda).integrate_points(c.pts, c.vox, c.valid, **kw)
+            torch.cuda.synchronize()
+            assert timing(True) == (0.0, 0)
+        assert timing(False) == (0.0, 0)
+        vol.brick_cull, vol.use_palette = True, True
+        _fuse(vol, sc.state, sc.im, 1.0)
+        assert timing(False) == (0.0, 0)
+    finally:
+        timing(False)
+        vol.brick_cull, vol.use_palette = True, True
+
+
 def test_a_restatement_reaches_the_edges(A):
     """The weighted scene-A reference really has what the comparison is about: skipped voxels of every bad kind,
     subnormal weights that update, capped and uncapped weights, waves that mix w_new == 1 with other weights."""
