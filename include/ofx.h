@@ -994,6 +994,59 @@ typedef struct ofx_gn_robust {
  * or a kernel with a scale that is not finite and > 0, is refused (OFX_ERR_ARG); device values are not checked. */
 int ofx_gn_set_robust(void* handle, const ofx_gn_robust* r);
 
+/* ---- motion completion network (OcclusionFusion's MotionCompleteNet, motion_model.py:7-98; inference only) ----
+ * The network that fills the solver's motion term (target_node_pos, node_conf): a 2-layer LSTM over each node's motion
+ * history, then a graph transformer over the 4-level pyramid of the ED graph, in f32; and the runner's pre- and
+ * post-processing (fusion_with_occlusion/run_motion_model.py:45-196) in f64. The LSTM and the Linear / LayerNorm layers
+ * are pinned to torch's own modules; the graph layers (TransformerConv, DeepGCNLayer 'res+') are restated from their
+ * definition and are unpinned against the reference. Yardstick: tests/motion_ref.py, in f64.
+ * (ABI 5: new entry points and a new struct, no existing struct changes.)
+ *
+ * ofx_motion_create: weights is a HOST pointer to the packed f32 blob that occlusionfusion_amd.motion.pack_weights
+ * builds (word 0 the layout tag, word 1 the length, both as uint32 bit patterns; then the tensors, transposed for the
+ * kernels). A wrong length or tag is OFX_ERR_ARG; max_nodes above 16384 is OFX_ERR_RANGE; max_hist in [1, 16].
+ * Synchronous (one host-to-device copy). */
+typedef struct ofx_motion_graph {
+  const int32_t* nn_index[4];  /* device, (n[l], k[l]) row-major: the neighbours of level l's nodes, -1 = none. Edge
+                                  (s, d): s the row, d the listed neighbour (run_motion_model.py:134-148); messages go
+                                  s -> d. An entry outside [0, n[l]) counts as -1; duplicates count twice */
+  int32_t n[4];                /* nodes per level, 1 .. max_nodes */
+  int32_t k[4];                /* list length per level, 1 .. 16 */
+  const int32_t* down[3];      /* device, down[l] (n[l+1]): the level-l node each level-(l+1) node is */
+  const int32_t* up[3];        /* device, up[l] (n[l]): the level-(l+1) node each level-l node reads coming back up.
+                                  Map entries are clamped into their range */
+} ofx_motion_graph;
+int ofx_motion_create(const float* weights, int64_t n_floats, int32_t max_nodes, int32_t max_hist, void** handle);
+int ofx_motion_destroy(void* handle);
+/* Copies the lists and maps (stream-ordered; the caller's arrays are free after the call's work has run) and builds on
+ * the device the incoming-edge CSR of every level, ordered by (target, source row, slot) — the edge-list order, so
+ * every sum over edges has one fixed order. No atomics, no host read. */
+int ofx_motion_set_graph(void* handle, const ofx_motion_graph* g, ofx_stream_t s);
+/* The network alone: pos f32 (N,3) centred positions, curr_motion f32 (N,4) [normalised motion | visible], hist f32
+ * (T,N,4), 1 <= T <= 16 -> out f32 (N,4) = (mu, sigma), sigma after softplus; out 16-byte aligned. N must be the
+ * graph's n[0] (else OFX_ERR_ARG; before ofx_motion_set_graph: OFX_ERR_STATE). 32 launches, two runs bitwise equal. */
+int ofx_motion_forward(void* handle, const float* pos, const float* curr_motion, const float* hist, int32_t T,
+                       int32_t n_nodes, float* out, ofx_stream_t s);
+/* One frame of the runner: src / dst f64 (N,3) node positions at the source frame and at the tracked estimate, visible
+ * u8 (N). Kabsch fit of the visible nodes (R the orthogonal polar factor of Hᵀ, no reflection fix), centimetres, std =
+ * mean of the visible rows' per-axis std + 0.1, the history (cap max_hist, rescaled by std_prev / std, new nodes
+ * appended as zeros, the previous-frame row from this call's and the last call's src), centred positions; the network;
+ * confidence = exp(-conf_scale (sigma / (|mu| + 1))²), node_motion = mu std / 100 + rigid motion. Outputs: node_motion
+ * f64 (N,3), confidence f64 (N), status i32 (1), and the network's inputs and raw output as they were used: pos_c f32
+ * (N,3), curr_motion f32 (N,4), hist f32 (T',N,4) with T' = min(calls since reset, max_hist), raw f32 (N,4). status
+ * bit 0: fewer than 3 visible nodes or a numerically singular H (|det H| <= 1e-12 |H|_F³): node_motion and confidence
+ * are 0 for every node, the history is still advanced (with no rigid part); bit 1: the same for the previous-frame fit
+ * (that history row then holds zero motion). N may grow between calls, never shrink (OFX_ERR_ARG). Stream-ordered,
+ * no host read; the handle's state (history, last src and visible, std) lives on the device. */
+int ofx_motion_complete(void* handle, const double* src, const double* dst, const uint8_t* visible, int32_t n_nodes,
+                        double conf_scale, double* node_motion, double* confidence, int32_t* status, float* pos_c,
+                        float* curr_motion, float* hist, float* raw, ofx_stream_t s);
+/* Forget the history: the next ofx_motion_complete is a first call. The graph stays. */
+int ofx_motion_reset(void* handle);
+/* info i64[10]: launches of the last forward, history rows held, nodes of the last call, max_nodes, n[0..3] of the
+ * graph (0 before ofx_motion_set_graph), max_hist, 0 */
+int ofx_motion_info(void* handle, int64_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ _EXPORTS = {
     "WarpField": "warpfield", "EDGraph": "warpfield",
     "GaussNewtonSolver": "registration", "Registration": "registration", "spd_solve": "registration",
     "FusionPipeline": "pipeline", "ProjectiveAssociator": "association", "SurfaceSampler": "surface",
-    "NodeGrower": "grow",
+    "NodeGrower": "grow", "MotionCompleter": "motion",
     "RigidAligner": "association", "fold_rigid": "association", "ModelRenderer": "association",
     "backproject_depth": "image_proc", "compute_mesh_from_depth": "image_proc", "depth_2_pc": "image_proc",
 }

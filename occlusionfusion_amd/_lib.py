@@ -94,6 +94,10 @@ class GnRobust(ctypes.Structure):
 ROBUST_KERNELS = {"none": 0, "huber": 1, "tukey": 2}   # OFX_ROBUST_* (include/ofx.h)
 
 
+class MotionGraph(ctypes.Structure):
+    _fields_ = [("nn_index", P * 4), ("n", c_int32 * 4), ("k", c_int32 * 4), ("down", P * 3), ("up", P * 3)]
+
+
 _SIGS = {
     "ofx_abi_version": [],
     "ofx_volume_num_slots": [P, P],
@@ -192,6 +196,13 @@ _SIGS = {
     "ofx_gn_share_history": [P, P],
     "ofx_gn_set_idle_hook": [P, P, P],
     "ofx_gn_set_robust": [P, P],
+    "ofx_motion_create": [P, c_int64, c_int32, c_int32, P],
+    "ofx_motion_destroy": [P],
+    "ofx_motion_set_graph": [P, P, P],
+    "ofx_motion_forward": [P, P, P, P, c_int32, c_int32, P, P],
+    "ofx_motion_complete": [P, P, P, P, c_int32, c_double, P, P, P, P, P, P, P, P],
+    "ofx_motion_reset": [P],
+    "ofx_motion_info": [P, P],
 }
 # the weighted integrate: an entry point's arguments with the ofx_obs_weights pointer in front of the stream
 for _name in ("ofx_integrate", "ofx_integrate_points", "ofx_integrate_palette", "ofx_integrate_palette_cull"):

@@ -761,7 +761,75 @@ def _(state, handle, match_weights, kernel, scale):
     return None
 
 
-OPS = ("integrate", "integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
+# --------------------------------------------------------------------------------------------- motion completion
+def _motion_rows(name, t, shape, dtype):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+
+
+@_op("motion_forward", mutates_args=("state",))
+def motion_forward(state: Tensor, handle: int, pos: Tensor, curr_motion: Tensor, hist: Tensor) -> Tensor:
+    """ofx_motion_forward (motion_model.py:52-98, inference): the motion completion network on the graph the handle holds
+    (ofx_motion_set_graph). pos f32 (N,3) centred node positions, curr_motion f32 (N,4) [normalised motion | visible],
+    hist f32 (T,N,4), 1 <= T <= 16 -> f32 (N,4) = (mu, sigma). `handle` is an ofx_motion_create handle; `state` is its
+    ordering token (its scratch is hidden state)."""
+    N, T = pos.shape[0], hist.shape[0]
+    _motion_rows("motion_forward: pos", pos, (N, 3), torch.float32)
+    _motion_rows("motion_forward: curr_motion", curr_motion, (N, 4), torch.float32)
+    _motion_rows("motion_forward: hist", hist, (T, N, 4), torch.float32)
+    out = torch.empty((N, 4), dtype=torch.float32, device=pos.device)
+    call("ofx_motion_forward", _lib.c_void_p(handle), ptr(pos), ptr(curr_motion), ptr(hist), T, N, ptr(out), _stream(pos))
+    return out
+
+
+@motion_forward.register_fake
+def _(state, handle, pos, curr_motion, hist):
+    return pos.new_empty((pos.shape[0], 4), dtype=torch.float32)
+
+
+@_op("motion_complete", mutates_args=("state",))
+def motion_complete(state: Tensor, handle: int, src: Tensor, dst: Tensor, visible: Tensor, conf_scale: float,
+                    max_hist: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """ofx_motion_complete (run_motion_model.py:45-196): one frame of the motion completion runner. src / dst f64 (N,3)
+    node positions at the source frame and at the tracked estimate, visible bool / u8 (N); conf_scale: 2 in the fusion
+    runner, 4 in demo.py; max_hist: the handle's (it sizes the history output). -> node_motion f64 (N,3), confidence f64
+    (N), status i32 (1) (bit 0: degenerate fit, outputs 0; bit 1: degenerate previous-frame fit), and the network's
+    inputs and raw output as used: pos f32 (N,3), curr_motion f32 (N,4), hist f32 (max_hist,N,4) of which the first
+    min(calls since reset, max_hist) rows are written (the rest 0), raw f32 (N,4). The history, the last src / visible
+    and the std live on the handle: `state` is its ordering token."""
+    N, dev = src.shape[0], src.device
+    _motion_rows("motion_complete: src", src, (N, 3), torch.float64)
+    _motion_rows("motion_complete: dst", dst, (N, 3), torch.float64)
+    if visible.dtype not in (torch.bool, torch.uint8) or tuple(visible.shape) != (N,):
+        raise ValueError(f"motion_complete: visible must be bool or uint8 of shape ({N},)")
+    info = (_lib.c_int64 * 10)()
+    call("ofx_motion_info", _lib.c_void_p(handle), info)
+    if int(max_hist) != info[8]:
+        raise ValueError(f"motion_complete: max_hist {max_hist} is not the handle's {info[8]}")
+    vis = visible.to(torch.uint8).contiguous()
+    node_motion = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    conf = torch.empty((N,), dtype=torch.float64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    pos = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    cm = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    hist = torch.zeros((int(max_hist), N, 4), dtype=torch.float32, device=dev)
+    raw = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    call("ofx_motion_complete", _lib.c_void_p(handle), ptr(src), ptr(dst), ptr(vis), N, float(conf_scale),
+         ptr(node_motion), ptr(conf), ptr(status), ptr(pos), ptr(cm), ptr(hist), ptr(raw), _stream(src))
+    return node_motion, conf, status, pos, cm, hist, raw
+
+
+@motion_complete.register_fake
+def _(state, handle, src, dst, visible, conf_scale, max_hist):
+    N = src.shape[0]
+    e = src.new_empty
+    return (e((N, 3), dtype=torch.float64), e((N,), dtype=torch.float64), e((1,), dtype=torch.int32),
+            e((N, 3), dtype=torch.float32), e((N, 4), dtype=torch.float32),
+            e((int(max_hist), N, 4), dtype=torch.float32), e((N, 4), dtype=torch.float32))
+
+
+OPS = ("integrate","integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
        "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate", "gn_set_robust",
-       "integrate_weighted", "integrate_points_weighted", "observation_weights")
+       "integrate_weighted", "integrate_points_weighted", "observation_weights", "motion_forward", "motion_complete")

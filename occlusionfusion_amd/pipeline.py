@@ -254,6 +254,17 @@ class FusionPipeline:
             conf = torch.cat([conf, torch.zeros(N - n, dtype=conf.dtype, device=conf.device)])
         return tpos, conf
 
+    def _visible_nodes(self):
+        """The nodes the last integrated frame sees (TSDFVolume.get_visible_nodes' check on the pipeline's own transforms,
+        fusion.py:143), bool (N) on the host; a pending overlapped integrate is enqueued and waited for first."""
+        self.flush()
+        if self.int_stream is not None:
+            torch.cuda.current_stream(self.device).wait_stream(self.int_stream)
+        if not hasattr(self.vol, "depth_t"):
+            raise ValueError("motion_net needs an integrated frame: integrate_source(fi) first")
+        dn = self.nodes_t if self.prev_trans is None else self.nodes_t + self.prev_trans
+        return self.vol.check_visibility(dn.to(torch.float32))[0]
+
     def _track_volume(self, fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters, assoc,
                       occ=(False, None, 0.01), depth_filter=None, grow_every=0, grow=None, photo=None, robust=None,
                       fusion=None):
@@ -309,7 +320,7 @@ class FusionPipeline:
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
                    max_model_points=65536, w_min=None, rigid_iters=0, occlusion=False, splat_radius=None,
                    occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, robust=None,
-                   fusion_weights=None, **assoc):
+                   fusion_weights=None, motion_net=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -363,7 +374,16 @@ class FusionPipeline:
         is built where the frame is staged, ahead of the solve, from the filtered frame's vertex and normal maps
         (`filter`; not shared with depth_filter's own ofx_prepare_depth call), and an overlapped integrate gets it with
         the depth and the colour. w_min=None is 1.0 without fusion weights and their w_floor with them (fractional
-        weights: 1.0 would empty the sampled model after the source frame); max_weight must not lie below it."""
+        weights: 1.0 would empty the sampled model after the source frame); max_weight must not lie below it.
+
+        motion_net (model="canonical"; None / a motion.MotionCompleter whose graph is set): the motion term comes from
+        the motion completion network instead of fi.tpos / fi.conf (fusion.py:142-151). The loop above runs with no
+        motion term; the nodes deformed at the previous frame and at the tracked estimate, with the previous frame's
+        visible nodes (TSDFVolume.get_visible_nodes: one host read, and a pending overlapped integrate is enqueued
+        first), go through the completer; one more association and solve (icp_iters=1, no rigid stage) runs from the
+        tracked transforms with target_node_pos = deformed_at_source + node_motion and node_conf = confidence. The
+        result carries "motion": {"node_motion", "confidence", "visible", "status"} (device tensors) and the log of
+        all the associations. None leaves the loop as it is."""
         from .association import photo_params
         from .registration import robust_params
         photo_params(photo)   # (an unknown key is a TypeError before anything is touched)
@@ -373,6 +393,8 @@ class FusionPipeline:
         if grow_every and model != "volume":
             raise ValueError("grow_every needs model='volume': the graph grows from the fused volume")
         if model == "volume":
+            if motion_net is not None:
+                raise ValueError("motion_net needs model='canonical'")
             return self._track_volume(fi, t, icp_iters, count_updates, motion, max_model_points, w_min, rigid_iters,
                                       assoc, (occlusion, splat_radius, occl_margin), depth_filter, grow_every, grow,
                                       photo, robust, fw)
@@ -393,13 +415,30 @@ class FusionPipeline:
         assoc.setdefault("max_matches", self.n_matches)
         self.vol.fusion_weights = fw
         self.vol.stage(fi.im)
-        out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
-                                fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
-                                self._motion(fi) if motion else None, icp_iters,
-                                rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
-                                depth_filter=depth_filter, robust=robust, **pho,
-                                **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),
-                                **assoc)
+        if motion_net is None:
+            out, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
+                                    fi.im[-1], self.intr, self.prev_rot, self.prev_trans,
+                                    self._motion(fi) if motion else None, icp_iters,
+                                    rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]),
+                                    depth_filter=depth_filter, robust=robust, **pho,
+                                    **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False),
+                                    **assoc)
+        else:
+            from .motion import motion_term
+            kw = dict(depth_filter=depth_filter, robust=robust, **pho,
+                      **self._occlusion(occlusion, splat_radius, occl_margin, pts.shape[0], fi.im[-1], False), **assoc)
+            first, log, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
+                                      fi.im[-1], self.intr, self.prev_rot, self.prev_trans, None, icp_iters,
+                                      rigid_iters=rigid_iters, rigid=self._rigid_aligner(rigid_iters, pts.shape[0]), **kw)
+            term, info = motion_term(motion_net, self.nodes_t, self.prev_trans, first["node_translations"],
+                                     self._visible_nodes())
+            out, log2, _ = icp_track(assoc_h, self.solver, self.nodes_t, self.edges_t, self.ew_t, pts, None, a, w, v,
+                                     fi.im[-1], self.intr, first["node_rotations"], first["node_translations"], term, 1,
+                                     **kw)
+            log = log + log2
+            out["motion"] = info
+            if "rigid" in first:
+                out["rigid"] = first["rigid"]
         out["assoc"] = log
         self.prev_rot, self.prev_trans = out["node_rotations"], out["node_translations"]
         self.last = out

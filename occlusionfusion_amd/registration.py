@@ -601,7 +601,7 @@ class Registration:
 
     def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
               rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, depth_filter=None, photo=None,
-              robust=None, **assoc):
+              robust=None, motion_net=None, **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -633,7 +633,14 @@ class Registration:
         without them a ValueError, before any device work. `mode` is ignored then: the target is always the vertex.
         None is the loop as it was.
         robust (None / "huber" / "tukey" / {"kernel", "scale"}): every solve of the loop runs with that robust kernel on
-        its data rows (GaussNewtonSolver.optimize's robust=); None is the loop as it was."""
+        its data rows (GaussNewtonSolver.optimize's robust=); None is the loop as it was.
+        motion_net (None / a motion.MotionCompleter whose graph is set): the motion term comes from the motion completion
+        network (fusion.py:142-151) instead of complete_node_motion_data: the loop runs with no motion term; the nodes
+        deformed at the source (graph.nodes + prev_trans) and at the tracked estimate, with the visible nodes of the
+        warp field's volume at its last frame (TSDFVolume.get_visible_nodes; a ValueError without a volume), go through
+        the completer; one more association and solve (icp_iters=1, no rigid stage) runs from the tracked transforms
+        with target_node_pos = deformed_at_source + node_motion and node_conf = confidence. The result then has
+        "motion": {"node_motion", "confidence", "visible", "status"}. None is the loop as it was."""
         robust_params(robust)   # (refused before anything is touched)
         from .association import (ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track,
                                   photo_params)
@@ -668,11 +675,28 @@ class Registration:
             if ren is None or ren.max_points < P or ren.max_pixels < n_pix:
                 self._renderer = ModelRenderer(P, n_pix, self.device)
             occ = dict(occlusion=True, renderer=self._renderer, splat_radius=splat_radius, occl_margin=occl_margin)
+        if motion_net is not None and getattr(self.warpfield, "tsdf", None) is None:
+            raise ValueError("motion_net needs the warp field's volume (its last frame gives the visible nodes)")
         out, log, _ = icp_track(self._assoc, self.solver, self.graph.nodes, self.graph.edges, self.graph.edges_weights,
                                 self.source_pcd, nrm, self.point_anchors, self.anchor_weight, None, depth,
-                                self._intr4(), self.prev_rot, self.prev_trans, complete_node_motion_data, icp_iters,
+                                self._intr4(), self.prev_rot, self.prev_trans,
+                                complete_node_motion_data if motion_net is None else None, icp_iters,
                                 rigid_iters=rigid_iters, rigid=getattr(self, "_rigid", None),
                                 depth_filter=depth_filter, robust=robust, **pho, **occ, **assoc)
+        minfo = None
+        if motion_net is not None:
+            from .motion import motion_term
+            first = out
+            term, minfo = motion_term(motion_net, self.graph.nodes, self.prev_trans, first["node_translations"],
+                                      self.warpfield.tsdf.get_visible_nodes())
+            out, log2, _ = icp_track(self._assoc, self.solver, self.graph.nodes, self.graph.edges,
+                                     self.graph.edges_weights, self.source_pcd, nrm, self.point_anchors,
+                                     self.anchor_weight, None, depth, self._intr4(), first["node_rotations"],
+                                     first["node_translations"], term, 1, depth_filter=depth_filter, robust=robust,
+                                     **pho, **occ, **assoc)
+            log = log + log2
+            if "rigid" in first:
+                out["rigid"] = first["rigid"]
         R, T = out["node_rotations"], out["node_translations"]
         self.prev_rot, self.prev_trans = R.clone(), T.clone()
         nodes_t = torch.as_tensor(self.graph.nodes, device=self.device)
@@ -686,6 +710,8 @@ class Registration:
             res["rigid"] = out["rigid"]
         if "render" in out:
             res["render"] = out["render"]
+        if minfo is not None:
+            res["motion"] = minfo
         return res
 
 
