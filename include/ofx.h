@@ -62,6 +62,10 @@
  *                           of the live frame, among the pixels that pass ofx_associate's gates — (no reference twin: the
  *                           reference's dense matches come from a learned flow network. Parity unpinned; restated op for
  *                           op by tests/photo_ref.py)
+ *   ofx_photo_refine        (new) sub-pixel refinement of ofx_photo_associate's matches: a translation-only inverse
+ *                           compositional Lucas-Kanade step over a small colour patch, and the vertex map interpolated at
+ *                           the refined pixel — (no reference twin: the reference's flow network is sub-pixel by itself.
+ *                           Parity unpinned; restated op for op by tests/refine_ref.py)
  *   ofx_depth_to_pc         Registration.optimize target cloud: depth_2_pc, NonRigidICP/model/geometry.py:44-59,
  *                           mask compaction, map_pixel_to_pcd              registration_fusion.py:104-109,388-395
  *   ofx_pixel_anchors_euclidean  csrc compute_pixel_anchors_euclidean     csrc/cpu/graph_proc.cpp:610-709
@@ -612,6 +616,68 @@ int ofx_photo_associate(void* assoc_handle, const float* points, const float* no
                         const ofx_photo_params* prm, uint8_t* code, float* tgt, float* warped, int32_t* pixel,
                         float* cost, int32_t* match_idx, float* src_out, float* tgt_out, int32_t* anchors_out,
                         float* weights_out, float* pixel_out, int32_t* count, ofx_stream_t s);
+
+/* ---------------- Sub-pixel refinement of photometric matches (new capability; the reference has none — parity unpinned) ----------------
+ * ofx_photo_associate picks a whole live pixel by the colour of one pixel. This call aligns the (2*half + 1)^2 colour patch
+ * around each match's place in a template image (the frame the point's colour came from) with the live frame, starting at the
+ * search's pixel: a classical Lucas-Kanade step, translation only, inverse compositional (template gradients, Hessian built
+ * once). The refined 3-D target is the vertex map interpolated at the refined pixel; it goes into the solver's existing 3-D
+ * rows. No handle, no allocation, no host sync; restated op for op by tests/refine_ref.py.
+ * Inputs (device): template_image f32 planar [3*H*W]; template_mask u8[H*W] or NULL (0 = masked; NULL = every pixel valid);
+ * color_image f32 planar [3*H*W] (the live frame); point_image f32 planar [3*H*W] (the live vertex map); template_px
+ * f32[R,2] (x, y) of each row's point in the template, sub-pixel; init_px f32[R,2] and tgt_in f32[R,3]: the search's
+ * pixel_out and tgt_out; count: DEVICE int32[2] as ofx_photo_associate writes it. The rows are 0 .. min(max(count[1], 0),
+ * max_rows) - 1, read on the device (the grid is sized from max_rows). Pixel (x, y) has its centre at integer coordinates.
+ * Arithmetic: every per-tap term is f32, one rounded operation per step, no contraction; every sum is f64 over exact
+ * products of two f32 values; the 2x2 solve is f64; u is kept as f32.
+ *   sample S(img, x, y): xf = floorf(x), yf = floorf(y); VALID iff 0 <= xf <= W - 2 and 0 <= yf <= H - 2 (all four neighbours
+ *         inside the image; NaN fails); fx = x - xf, fy = y - yf; with p00 = img[yf][xf], p10 = img[yf][xf + 1], p01 =
+ *         img[yf + 1][xf], p11 = img[yf + 1][xf + 1]: S = (1 - fy)*((1 - fx)*p00 + fx*p10) + fy*((1 - fx)*p01 + fx*p11).
+ *         A template sample is valid only if, besides, none of its four neighbours is masked.
+ *   taps: d = (dx, dy), dy = -half..half (outer), dx = -half..half (inner); n_taps = (2*half + 1)^2; three channels each
+ *   template, once: T(d) = S(template, tx + (float)dx, ty + (float)dy); g_x(d) = 0.5*(T(d + (1,0)) - T(d - (1,0))), g_y(d) =
+ *         0.5*(T(d + (0,1)) - T(d - (0,1))), each neighbour sampled at t + (float)(d +- 1) itself;
+ *         Hxx = sum g_x*g_x, Hxy = sum g_x*g_y, Hyy = sum g_y*g_y over taps (outer) and channels (inner);
+ *         det = Hxx*Hyy - Hxy*Hxy; lmin = 0.5*((Hxx + Hyy) - sqrt((Hxx - Hyy)^2 + 4*(Hxy*Hxy)))
+ *   iteration k = 0 .. iters - 1, from u = init_px: r(d) = S(color_image, u_x + (float)dx, u_y + (float)dy) - T(d);
+ *         b_x = sum g_x*r, b_y = sum g_y*r; D_x = (Hyy*b_x - Hxy*b_y)/det, D_y = (Hxx*b_y - Hxy*b_x)/det;
+ *         u_x = (float)((double)u_x - D_x), u_y likewise; the row freezes (no further iteration) once |D_x| < eps and
+ *         |D_y| < eps, after that update
+ *   residual, after the last iteration: r(d) at the final u once more; msr = (sum r*r)/(3*n_taps); ssd = (float)msr
+ *   target: tgt = S(point_image plane, u_x, u_y) for the three planes
+ * The device sums each lane's taps in order and then the lanes of a row's group in a fixed xor tree, the restatement in tap
+ * order: the f64 sums may differ in their last bits, nothing else does. Two calls give the same bytes.
+ * status u8[R], the first code that applies (in the order the steps run):
+ *   1  init_px or template_px non-finite, or init_px == (-1, -1)
+ *   2  a template sample (the +-1 gradient samples included) is off the image or touches a masked pixel
+ *   3  !(det > 0), or !(lmin/n_taps >= min_eig)
+ *   4  a live sample is off the image in some iteration or in the residual pass
+ *   5  max(|u_x - init_x|, |u_y - init_y|) > max_shift (f32) after some iteration's update
+ *   6  !(msr <= ssd_max^2) (f64; +inf switches it off; a NaN lands here)
+ *   7  one of the four vertex-map neighbours of the final u has !(z > 0), or !(max z - min z <= edge_max)
+ *   0  refined
+ * Outputs, every row below the count written on every call: px_out f32[R,2] and tgt_out f32[R,3] — the refined u and tgt on
+ * status 0, init_px and tgt_in copied otherwise; status; ssd f32[R] — (float)msr for status 0, 6 and 7, 0 otherwise. Rows at
+ * or past the count are left untouched; a count of 0 is legal. px_out / tgt_out may not alias init_px / tgt_in.
+ * OFX_ERR_ARG, before any device work: null params / count, a null or misaligned buffer (max_rows > 0), half outside
+ * [1, OFX_REFINE_HMAX], iters < 1, a negative or non-finite eps, max_shift, min_eig or edge_max, a NaN ssd_max, height or
+ * width < 1, max_rows < 0. Stream-ordered. */
+typedef struct ofx_refine_params {
+  int32_t half;              /* 1 .. OFX_REFINE_HMAX: patch (2*half + 1)^2 */
+  int32_t iters;             /* >= 1 */
+  float eps;                 /* px: a row freezes once both |D| < eps */
+  float max_shift;           /* px: status 5 beyond it (Chebyshev distance from init_px) */
+  float min_eig;             /* status 3 below it: smaller eigenvalue of H per tap */
+  float ssd_max;             /* status 6 if the mean squared residual exceeds ssd_max^2 (+inf: off) */
+  float edge_max;            /* m: ofx_associate's depth-edge gate at the refined pixel's four neighbours */
+  int32_t _pad;
+} ofx_refine_params;
+#define OFX_REFINE_HMAX 4
+int ofx_photo_refine(const float* template_image, const uint8_t* template_mask, const float* color_image,
+                     const float* point_image, const float* template_px, const float* init_px, const float* tgt_in,
+                     const int32_t* count, int32_t max_rows, int32_t height, int32_t width,
+                     const ofx_refine_params* prm, float* px_out, float* tgt_out, uint8_t* status, float* ssd,
+                     ofx_stream_t s);
 
 /* ---------------- Skinned surface points of the TSDF (new capability; the reference has none — parity unpinned) ----------------
  * The tracking model read off the volume itself: canonical surface points, their outward normals and their anchors and

@@ -39,6 +39,14 @@ class PhotoParams(ctypes.Structure):
 PHOTO_RMAX = 8   # OFX_PHOTO_RMAX (include/ofx.h)
 
 
+class RefineParams(ctypes.Structure):
+    _fields_ = [("half", c_int32), ("iters", c_int32), ("eps", c_float), ("max_shift", c_float), ("min_eig", c_float),
+                ("ssd_max", c_float), ("edge_max", c_float), ("_pad", c_int32)]
+
+
+REFINE_HMAX = 4   # OFX_REFINE_HMAX (include/ofx.h)
+
+
 class RigidParams(ctypes.Structure):
     _fields_ = [("dist_max", c_float), ("cos_min", c_float), ("edge_max", c_float), ("iters", c_int32),
                 ("min_matches", c_int32), ("damping", c_double), ("stop_twist", c_double)]
@@ -144,6 +152,7 @@ _SIGS = {
     "ofx_associate": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P],
     "ofx_photo_associate": [P, P, P, P, P, P, P, c_int64, P, c_int32, P, P, P, P, c_int32, c_int32, P, P, P, P, P, P, P, P, P,
                             P, P, P, P, P],
+    "ofx_photo_refine": [P, P, P, P, P, P, P, P, c_int32, c_int32, c_int32, P, P, P, P, P, P],
     "ofx_rigid_create": [c_int64, P],
     "ofx_rigid_destroy": [P],
     "ofx_rigid_icp": [P, P, P, P, P, P, c_int64, P, c_int32, P, P, c_int32, c_int32, P, P, P, P, P],

@@ -13,7 +13,9 @@ live frame: with occlusion=True, icp_track keeps the points that the model itsel
 WarpField.render_live shows the fused model where the camera is. ProjectiveAssociator.associate_photo
 (torch.ops.ofx.photo_associate -> ofx_photo_associate) is the search by colour — the stand-in for the reference's flow
 net: with photo=True, icp_track matches every point to the best colour match in a window around its pixel, which follows
-motion along a surface that depth alone cannot see.
+motion along a surface that depth alone cannot see. ProjectiveAssociator.refine_photo (torch.ops.ofx.photo_refine ->
+ofx_photo_refine) makes those whole-pixel matches sub-pixel: with photo_refine=True and a template, icp_track aligns a
+small colour patch of the template around each match and takes the vertex map at the refined pixel as the target.
 """
 import numpy as np
 import torch
@@ -26,6 +28,8 @@ CODE_NAMES = ("accepted", "invalid_skin", "off_image", "hole", "no_normal", "too
 PHOTO_CODE_NAMES = CODE_NAMES + ("colour",)   # associate_photo's codes: associate's, and 7
 ASSOC_DEFAULTS = dict(dist_max=0.05, cos_min=0.5, edge_max=0.03, mode="plane", max_matches=10000)
 PHOTO_DEFAULTS = dict(radius=4, color_max=float("inf"), geo_weight=1.0)
+REFINE_DEFAULTS = dict(half=3, iters=8, eps=1e-3, max_shift=4.0, min_eig=1e-6, ssd_max=float("inf"))
+REFINE_CODE_NAMES = ("refined", "no_match", "template_off", "flat", "left_image", "too_far", "residual", "depth_edge")
 
 
 class TooFewMatches(RuntimeError):
@@ -148,7 +152,7 @@ class ProjectiveAssociator(_Handle):
 
         Returns associate's dict (code 7 = "colour": PHOTO_CODE_NAMES; the histogram has one more entry), plus pixel
         (emitted rows, f32 (u, v) of the match: what the solver's target_px / target_py take), pixel_all i32 (P,2) and
-        cost (P,). The same single host read."""
+        cost (P,) and count (the device int32[2] = [accepted, emitted]). The same single host read."""
         d = self.device
         pts, nrm, a, w, v, packed, P = _skinned(points, normals, anchors, weights, valid, warpfield_or_packed_nodes, d,
                                                 self.max_points, "associator")
@@ -165,9 +169,46 @@ class ProjectiveAssociator(_Handle):
         n_acc, n_emit = int(host[0]), int(host[1])
         self.last = {"match_idx": midx[:n_emit], "src": src[:n_emit], "tgt": tgt[:n_emit], "anchors": a_o[:n_emit],
                      "weights": w_o[:n_emit], "pixel": px_o[:n_emit], "code": code, "tgt_all": tgt_all,
-                     "warped": warped, "pixel_all": pixel_all, "cost": cost, "accepted": n_acc, "emitted": n_emit,
+                     "warped": warped, "pixel_all": pixel_all, "cost": cost, "count": count, "accepted": n_acc,
+                     "emitted": n_emit,
                      "histogram": [int(x) for x in host[2:2 + len(PHOTO_CODE_NAMES)]]}
         return self.last
+
+
+    def refine_photo(self, match, template_image, template_px, color_image, point_image, edge_max,
+                     template_mask=None, **refine):
+        """Sub-pixel refinement of associate_photo's emitted matches (torch.ops.ofx.photo_refine -> ofx_photo_refine):
+        `match` is associate_photo's result; template_image (3,H,W) rgb is the frame the model's colours came from,
+        template_px f32 (rows,2) the (x, y) place of each emitted row's point in it (sub-pixel), template_mask (H,W) an
+        optional validity mask of its pixels; color_image / point_image are the live frame's, as given to
+        associate_photo; edge_max is the association's depth-edge gate, applied at the refined pixel. **refine:
+        REFINE_DEFAULTS' keys. The (2·half + 1)² patch around template_px is aligned with the live frame from the
+        match's pixel by `iters` translation-only inverse compositional Lucas-Kanade steps; a row that cannot be refined
+        keeps its whole-pixel match.
+
+        Returns the match dict with tgt and pixel replaced, plus refine_status u8 (REFINE_CODE_NAMES) and refine_ssd
+        (the mean squared colour residual at the refined pixel). All device tensors; nothing is read back."""
+        prm = refine_params(refine or True)
+        d = self.device
+        n = int(match["emitted"])
+        tim, cim, vm = _f32(template_image, d), _f32(color_image, d), _f32(point_image, d)
+        tpx = _f32(template_px, d, (n, 2))
+        ipx, tgt = match["pixel"].contiguous(), match["tgt"].contiguous()
+        mask = None
+        if template_mask is not None:
+            mask = template_mask if isinstance(template_mask, torch.Tensor) else torch.as_tensor(
+                np.ascontiguousarray(template_mask))
+            mask = mask.to(device=d)
+        count = match["count"]   # the search's device [accepted, emitted]: the rows are read from it on the device
+        px_o, tgt_o = torch.empty_like(ipx), torch.empty_like(tgt)
+        status = torch.empty(n, dtype=torch.uint8, device=d)
+        ssd = torch.empty(n, dtype=torch.float32, device=d)
+        torch.ops.ofx.photo_refine(tim, mask, cim, vm, tpx, ipx, tgt, count, int(prm["half"]), int(prm["iters"]),
+                                   float(prm["eps"]), float(prm["max_shift"]), float(prm["min_eig"]),
+                                   float(prm["ssd_max"]), float(edge_max), px_o, tgt_o, status, ssd)
+        out = dict(match)
+        out.update(tgt=tgt_o, pixel=px_o, refine_status=status, refine_ssd=ssd)
+        return out
 
 
 class RigidAligner(_Handle):
@@ -312,10 +353,26 @@ def photo_params(photo):
     return pho
 
 
+def refine_params(refine):
+    """The photo_refine= keyword of the tracking layers as refine_photo's keywords, with photo_params' conventions: None
+    / False -> None (off), True -> REFINE_DEFAULTS, a dict of half / iters / eps / max_shift / min_eig / ssd_max -> the
+    defaults with those; another key is a TypeError."""
+    if refine is None or refine is False:
+        return None
+    prm = dict(REFINE_DEFAULTS)
+    if refine is not True:
+        unknown = set(refine) - set(prm)
+        if unknown:
+            raise TypeError(f"unknown photo_refine parameters {sorted(unknown)}")
+        prm.update(refine)
+    return prm
+
+
 def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights, points, normals, anchors, weights,
               valid, depth, intr, prev_rot=None, prev_trans=None, complete_node_motion_data=None, icp_iters=3,
               rigid_iters=0, rigid=None, occlusion=False, renderer=None, splat_radius=None, occl_margin=0.01,
-              depth_filter=None, photo=None, colors=None, color_image=None, robust=None, **assoc):
+              depth_filter=None, photo=None, colors=None, color_image=None, robust=None, photo_refine=None,
+              template=None, **assoc):
     """Track one depth frame without given matches: backproject depth (H,W) to the vertex map, then icp_iters times
     associate the points under the current estimate (prev_rot / prev_trans, None = identity) and solve on the emitted
     matches from that estimate (solver.optimize). Without motion data the nodes are their own targets with confidence
@@ -351,6 +408,13 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     one bit for bit), the filter's settings with it. `mode` is ignored under photo: the target is always the vertex.
     The rigid stage and the occlusion gate work as before.
 
+    photo_refine: None — the loop as it was; True, or a dict of half / iters / eps / max_shift / min_eig / ssd_max
+    (REFINE_DEFAULTS; another key is a TypeError) — every iteration refines the search's emitted matches before the solve
+    (ProjectiveAssociator.refine_photo): the targets become sub-pixel. It needs photo and `template` = (image (3,H,W),
+    px (P,2): the (x, y) place of every model point in that image, optional mask (H,W)) — the frame the model's colours
+    came from (a ValueError without either, before any device work). The template pixel of emitted row i is
+    px[match_idx[i]]; edge_max is the association's. No host read is added.
+
     robust: None — the loop as it was; "huber", "tukey" or a dict of kernel / scale (registration.ROBUST_DEFAULTS; another
     key is a TypeError, an unknown kernel a ValueError, before any device work) — forwarded to every solver.optimize of
     the loop: an M-estimator on the data rows, so a match just inside dist_max no longer pulls like a perfect one."""
@@ -378,6 +442,12 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
     pho = photo_params(photo)
     if pho is not None and (colors is None or color_image is None):
         raise ValueError("photo needs the model's colours (colors=...) and the frame's colour image (color_image=...)")
+    ref = refine_params(photo_refine)
+    if ref is not None and pho is None:
+        raise ValueError("photo_refine refines the photometric search's matches: it needs photo=...")
+    if ref is not None and template is None:
+        raise ValueError("photo_refine needs the template (template=(image, px, mask or None)): the frame the model's "
+                         "colours came from and every model point's pixel in it")
     d = solver.device
     prm = dict(ASSOC_DEFAULTS)
     unknown = set(assoc) - set(prm)
@@ -401,6 +471,11 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         vm = backproject_depth_device(dep, fx, fy, cx, cy)
     else:
         vm = prepare_depth_device(dep, fx, fy, cx, cy, normals=False, **filt)["point_image"]
+    if ref is not None:
+        t_im, t_px = _f32(template[0], d), _f32(template[1], d, (-1, 2))
+        t_mask = template[2] if len(template) > 2 else None
+        if t_im.shape != vm.shape:
+            raise ValueError(f"the template image must be {tuple(vm.shape)}, got {tuple(t_im.shape)}")
     tloc, tconf = complete_node_motion_data if complete_node_motion_data is not None else (None, None)
     rot, trans, out, log = prev_rot, prev_trans, None, []
     rig = None
@@ -441,6 +516,8 @@ def icp_track(associator, solver, graph_nodes, graph_edges, graph_edges_weights,
         if m["emitted"] < 16:
             raise TooFewMatches(f"projective association {it} emitted {m['emitted']} matches of {m['accepted']} accepted "
                                 f"({dict(zip(PHOTO_CODE_NAMES, m['histogram']))}); at least 16 (4·K) are needed to solve")
+        if ref is not None:
+            m = associator.refine_photo(m, t_im, t_px[m["match_idx"].long()], cim, vm, prm["edge_max"], t_mask, **ref)
         out = solver.optimize(graph_nodes, graph_edges, graph_edges_weights, tloc, tconf, m["src"], m["anchors"],
                               m["weights"], m["tgt"], (fx, fy, cx, cy), prev_rot=rot, prev_trans=trans, **rob)
         rot, trans = out["node_rotations"], out["node_translations"]

@@ -373,6 +373,48 @@ def _(state, handle, points, normals, colors, anchors, weights, valid, packed_no
             points.new_empty((2,), dtype=i))
 
 
+# --------------------------------------------------------------------------------------------- sub-pixel match refinement
+@_op("photo_refine", mutates_args=("px_out", "tgt_out", "status", "ssd"))
+def photo_refine(template_image: Tensor, template_mask: Optional[Tensor], color_image: Tensor, point_image: Tensor,
+                 template_px: Tensor, init_px: Tensor, tgt_in: Tensor, count: Tensor, half: int, iters: int, eps: float,
+                 max_shift: float, min_eig: float, ssd_max: float, edge_max: float, px_out: Tensor, tgt_out: Tensor,
+                 status: Tensor, ssd: Tensor) -> None:
+    """ofx_photo_refine (new capability, no reference twin): the translation-only inverse compositional Lucas-Kanade
+    refinement of photo_associate's matches. template_image / color_image / point_image f32 (3,H,W); template_mask u8 or
+    bool (H,W) or None; template_px / init_px f32 (R,2); tgt_in f32 (R,3); count: photo_associate's int32[2] on the
+    device (the rows are the first min(count[1], R)). Written in place for those rows, the rest left untouched: px_out
+    f32 (R,2), tgt_out f32 (R,3), status u8 (R,), ssd f32 (R,). No handle, no hidden state."""
+    R = init_px.shape[0]
+    _, H, W = color_image.shape
+    f = torch.float32
+    if template_image.shape != color_image.shape or point_image.shape != color_image.shape or color_image.shape[0] != 3:
+        raise ValueError("photo_refine: template, colour and point image must all be (3, H, W)")
+    for name, t, shape, dt in (("template_image", template_image, (3, H, W), f), ("color_image", color_image, (3, H, W), f),
+                               ("point_image", point_image, (3, H, W), f), ("template_px", template_px, (R, 2), f),
+                               ("init_px", init_px, (R, 2), f), ("tgt_in", tgt_in, (R, 3), f),
+                               ("count", count, (2,), torch.int32), ("px_out", px_out, (R, 2), f),
+                               ("tgt_out", tgt_out, (R, 3), f), ("status", status, (R,), torch.uint8),
+                               ("ssd", ssd, (R,), f)):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"photo_refine: {name} must be a contiguous {dt} tensor of shape {shape}")
+    m = None
+    if template_mask is not None:
+        if tuple(template_mask.shape) != (H, W):
+            raise ValueError(f"photo_refine: template_mask must be ({H}, {W})")
+        m = template_mask.to(torch.uint8).contiguous()
+    prm = _lib.RefineParams(int(half), int(iters), float(eps), float(max_shift), float(min_eig), float(ssd_max),
+                            float(edge_max), 0)
+    call("ofx_photo_refine", ptr(template_image), ptr(m), ptr(color_image), ptr(point_image), ptr(template_px),
+         ptr(init_px), ptr(tgt_in), ptr(count), R, H, W, byref(prm), ptr(px_out), ptr(tgt_out), ptr(status), ptr(ssd),
+         _stream(init_px))
+
+
+@photo_refine.register_fake
+def _(template_image, template_mask, color_image, point_image, template_px, init_px, tgt_in, count, half, iters, eps,
+      max_shift, min_eig, ssd_max, edge_max, px_out, tgt_out, status, ssd):
+    return None
+
+
 # --------------------------------------------------------------------------------------------- rigid pre-alignment
 @_op("rigid_icp", mutates_args=("state", "pose"))
 def rigid_icp(state: Tensor, handle: int, points: Tensor, normals: Optional[Tensor], anchors: Tensor, weights: Tensor,
@@ -832,4 +874,4 @@ def _(state, handle, src, dst, visible, conf_scale, max_hist):
 OPS = ("integrate","integrate_points", "raycast", "skin_points", "deform_points", "gn_solve", "gn_prepare", "gn_setup",
        "gn_linearize", "gn_step", "gn_finish", "spd_solve", "associate", "surface_points",
        "rigid_icp", "splat_points", "prepare_depth", "grow_nodes", "photo_associate", "gn_set_robust",
-       "integrate_weighted", "integrate_points_weighted", "observation_weights", "motion_forward", "motion_complete")
+       "integrate_weighted", "integrate_points_weighted", "observation_weights", "motion_forward", "motion_complete", "photo_refine")

@@ -87,6 +87,21 @@ class FusionPipeline:
         "canonical", photo=...) colours the canonical points with, at their own pixels."""
         self._source_rgb = im[:3]
         self._ccolors = None
+        self._ctemplate = None
+
+    def _canonical_template(self):
+        """track_step(model="canonical", photo_refine=...)'s template: the source frame's rgb (3,H,W) on the device and
+        (P,2) f32, each canonical point's own (x, y) projection into it (sub-pixel), computed once. No mask."""
+        if getattr(self, "_ctemplate", None) is None:
+            rgb = self._source_rgb
+            rgb = rgb if isinstance(rgb, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rgb, np.float32))
+            rgb = rgb.to(self.device, torch.float32).contiguous()
+            p = torch.from_numpy(np.ascontiguousarray(self.seq.canonical_points, np.float32)).to(self.device)
+            fx, fy, cx, cy = (float(x) for x in self.intr[:4])
+            z = p[:, 2].clamp(min=1e-6)
+            px = torch.stack([p[:, 0] * fx / z + cx, p[:, 1] * fy / z + cy], 1).contiguous()
+            self._ctemplate = (rgb, px, None)
+        return self._ctemplate
 
     def _canonical_colors(self):
         """(P,3) f32 rgb of seq.canonical_points: the source frame's colour at each point's pixel (the rounded
@@ -320,7 +335,7 @@ class FusionPipeline:
     def track_step(self, fi, t, icp_iters=3, count_updates=False, motion=True, model="canonical",
                    max_model_points=65536, w_min=None, rigid_iters=0, occlusion=False, splat_radius=None,
                    occl_margin=0.01, depth_filter=None, grow_every=0, grow=None, photo=None, robust=None,
-                   fusion_weights=None, motion_net=None, **assoc):
+                   fusion_weights=None, motion_net=None, photo_refine=None, **assoc):
         """step() without given matches (optional; step / solve / prepare are untouched): frame fi's depth is tracked
         by projective association of the pipeline's canonical points (seq.canonical_points, skinned once) and
         icp_iters GN solves (association.icp_track: fi's matches are not read; fi.tpos / fi.conf are the motion term
@@ -366,6 +381,12 @@ class FusionPipeline:
         pixels (set_source_colors(im), called by integrate_source; a ValueError without it, before any device work).
         `mode` is ignored then: the target is always the vertex. None leaves the loop as it is.
 
+        photo_refine (model="canonical"; None / True / a dict of half, iters, eps, max_shift, min_eig, ssd_max; needs
+        photo): every association's emitted matches are refined to sub-pixel before the solve
+        (ProjectiveAssociator.refine_photo): the template is the source frame's rgb (kept by set_source_colors) and each
+        canonical point's template pixel is its own projection into the source frame. model="volume" is a ValueError: a
+        template of the rendered model is not built. None leaves the loop as it is.
+
         robust (both models; None / "huber" / "tukey" / {"kernel", "scale"}): every solve of the tracking loop runs with
         that robust kernel on its data rows (GaussNewtonSolver.optimize's robust=). None leaves the loop as it is.
 
@@ -384,9 +405,15 @@ class FusionPipeline:
         tracked transforms with target_node_pos = deformed_at_source + node_motion and node_conf = confidence. The
         result carries "motion": {"node_motion", "confidence", "visible", "status"} (device tensors) and the log of
         all the associations. None leaves the loop as it is."""
-        from .association import photo_params
+        from .association import photo_params, refine_params
         from .registration import robust_params
         photo_params(photo)   # (an unknown key is a TypeError before anything is touched)
+        if refine_params(photo_refine) is not None:
+            if model == "volume":
+                raise ValueError("photo_refine with model='volume': the template of the rendered model is not built "
+                                 "(use model='canonical')")
+            if photo_params(photo) is None:
+                raise ValueError("photo_refine refines the photometric search's matches: it needs photo=...")
         robust_params(robust)
         fw = fusion_weight_params(fusion_weights) if fusion_weights is not None else getattr(self, "fusion_weights", None)
         w_min = resolve_w_min(w_min, fw)   # (a ValueError for a cap below it, before any device work)
@@ -407,6 +434,8 @@ class FusionPipeline:
                 raise ValueError("photo needs the model's colours: integrate_source(fi) (or set_source_colors(im)) "
                                  "takes them from the source frame")
             pho = dict(photo=photo, colors=self._canonical_colors(), color_image=fi.im[:3])
+            if refine_params(photo_refine) is not None:
+                pho.update(photo_refine=photo_refine, template=self._canonical_template())
         if getattr(self, "_track", None) is None:
             pts = torch.from_numpy(np.ascontiguousarray(self.seq.canonical_points, np.float32)).to(self.device)
             a, w, v = self.wf.skin_device(pts)

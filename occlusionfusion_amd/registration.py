@@ -507,9 +507,12 @@ class Registration:
         self.prev_trans = None
         self.update(canonical_vertices)
 
-    def update(self, canonical_vertices, colors=None):
+    def update(self, canonical_vertices, colors=None, template=None):
         """registration_fusion.py:66-85: skin the canonical vertices, keep the valid ones. colors: optional rgb in [0,1]
-        of the vertices, (V,3): kept for the valid ones as source_colors, what track(photo=...) matches with."""
+        of the vertices, (V,3): kept for the valid ones as source_colors, what track(photo=...) matches with. template:
+        optional (image (3,H,W) rgb, px (V,2): every vertex's (x, y) place in it, sub-pixel, optional mask (H,W)) — the
+        frame the colours came from: kept, with the valid vertices' px, as source_template, what track(photo_refine=...)
+        refines the matches against."""
         a, w, v = self.warpfield.skin_device(canonical_vertices)
         self.valid_source_verts = v.cpu().numpy()
         vt = torch.as_tensor(np.ascontiguousarray(canonical_vertices, np.float32), device=self.device)
@@ -521,6 +524,10 @@ class Registration:
         if colors is not None:
             self.source_colors = torch.as_tensor(np.ascontiguousarray(colors, np.float32),
                                                  device=self.device).reshape(-1, 3)[v]
+        self.source_template = None
+        if template is not None:
+            px = torch.as_tensor(np.ascontiguousarray(template[1], np.float32), device=self.device).reshape(-1, 2)[v]
+            self.source_template = (template[0], px, template[2] if len(template) > 2 else None)
 
     def update_from_volume(self, max_points=None, w_min=1.0):
         """The model from the fused volume instead of caller-given vertices (the reference's per-frame
@@ -536,6 +543,7 @@ class Registration:
             max_points = wf.surface_points(0, w_min)["accepted"]
         m = wf.surface_points(int(max_points), w_min)
         self.source_colors = wf.surface_colors(m) if getattr(wf.tsdf, "with_color", False) else None
+        self.source_template = None   # (a template of the rendered model is not built)
         self.source_pcd = m["points"].clone()
         self.point_anchors = m["anchors"].clone()
         self.anchor_weight = m["weights"].clone()
@@ -601,7 +609,7 @@ class Registration:
 
     def track(self, target_frame_data, complete_node_motion_data=None, source_normals=None, icp_iters=3,
               rigid_iters=0, occlusion=False, splat_radius=None, occl_margin=0.01, depth_filter=None, photo=None,
-              robust=None, motion_net=None, **assoc):
+              robust=None, motion_net=None, photo_refine=None, **assoc):
         """Register the target depth frame without given matches (no reference twin: the reference's matches come from
         learned front-ends). target_frame_data: {"im": (6,H,W) image, depth last, optional "id"}. The depth is
         backprojected to the vertex map (and tgt_pcd / pix_2_pcd are set as optimize does); then icp_iters times:
@@ -632,6 +640,10 @@ class Registration:
         model's colours are source_colors (update(colors=...), or update_from_volume() of a volume that fuses colour):
         without them a ValueError, before any device work. `mode` is ignored then: the target is always the vertex.
         None is the loop as it was.
+        photo_refine (None / True / a dict of half, iters, eps, max_shift, min_eig, ssd_max; needs photo): every
+        association's emitted matches are refined to sub-pixel before the solve (ProjectiveAssociator.refine_photo,
+        ofx_photo_refine) against source_template (update(vertices, colors=, template=)): without photo or without the
+        template a ValueError, before any device work. None is the loop as it was.
         robust (None / "huber" / "tukey" / {"kernel", "scale"}): every solve of the loop runs with that robust kernel on
         its data rows (GaussNewtonSolver.optimize's robust=); None is the loop as it was.
         motion_net (None / a motion.MotionCompleter whose graph is set): the motion term comes from the motion completion
@@ -643,13 +655,21 @@ class Registration:
         "motion": {"node_motion", "confidence", "visible", "status"}. None is the loop as it was."""
         robust_params(robust)   # (refused before anything is touched)
         from .association import (ModelRenderer, ProjectiveAssociator, RigidAligner, default_splat_radius, icp_track,
-                                  photo_params)
+                                  photo_params, refine_params)
         pho = {}
+        if refine_params(photo_refine) is not None:
+            if photo_params(photo) is None:
+                raise ValueError("photo_refine refines the photometric search's matches: it needs photo=...")
+            if getattr(self, "source_template", None) is None:
+                raise ValueError("photo_refine needs the template: update(vertices, colors=..., template=(image, px, "
+                                 "mask or None))")
         if photo_params(photo) is not None:
             if getattr(self, "source_colors", None) is None:
                 raise ValueError("photo needs the model's colours: update(vertices, colors=...) or update_from_volume() "
                                  "of a volume that fuses colour")
             pho = dict(photo=photo, colors=self.source_colors, color_image=target_frame_data["im"][:3])
+            if refine_params(photo_refine) is not None:
+                pho.update(photo_refine=photo_refine, template=self.source_template)
         depth = torch.as_tensor(np.ascontiguousarray(target_frame_data["im"][-1], np.float32), device=self.device)
         self.tgt_pcd, self.pix_2_pcd = depth_2_pc_device(depth, self.intrinsics)
         P = self.source_pcd.shape[0]
